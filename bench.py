@@ -9,16 +9,21 @@ A benchmark "step" is ONE Langevin step of the whole batch: score network forwar
 gradient, noise, update, NMSE log.  Every one of the 6933 steps of the schedule is the same work (the noise level only
 changes three scalars), so
     channels/s = trajectories / (6933 * seconds_per_step)
-is the full-schedule rate; `--full-schedule` walks all 6933 steps instead of K to confirm it, and every default run also
-times a sustained segment (`--sustained`, 1000 steps) after the K-step window and reports it next to the headline.
+is the full-schedule rate; `--full-schedule` walks all 6933 steps instead of K to confirm it.
+
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else.  `--full` adds every other
+measurement after the K-step window: a sustained segment (`--sustained`, 1000 steps), the other launch mode, the
+per-kernel roofline, the exact mode (bf16x3), the strong-scaling workloads and the CPU baseline.  `--dump-outputs DIR`
+writes what the timed path computed in its last step (rank 0's channel estimates and NMSE) as DIR/<name>.npy; the
+inputs are seeded, so two builds can be compared output for output.
 
 `python bench.py --gpus N` starts its own N ranks (one process per GPU, torch.distributed over RCCL) when it is not
 already running under torch.distributed.run; the parent never touches the GPU.  Trajectories are independent: the weak
-number gives every rank its own 1700 trajectories, and the same run also times the STRONG-scaling workload -- the
-20 400 trajectories of the tune_hparams_score grid (12 (alpha, beta) cells x 17 SNR x 100 channels, BASELINE configs[2])
-sharded over the ranks by shard.my_block -- reported as the `strong` object.  The only collective is the final gather of
-the per-step NMSE curves.  `--workload big` runs BASELINE configs[4] instead (Nt256 x Nr64, 1024 trajectories, fp16
-weights).  Prints ONE JSON line on rank 0.
+number gives every rank its own 1700 trajectories, and with `--full` the same run also times the STRONG-scaling
+workload -- the 20 400 trajectories of the tune_hparams_score grid (12 (alpha, beta) cells x 17 SNR x 100 channels,
+BASELINE configs[2]) sharded over the ranks by shard.my_block -- reported as the `strong` object.  The only collective is
+the final gather of the per-step NMSE curves.  `--workload big` runs BASELINE configs[4] instead (Nt256 x Nr64, 1024
+trajectories, fp16 weights).  Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -40,6 +45,7 @@ PEAK_HBM_TBS = 8.0                 # HBM3E spec (6.3 TB/s achievable by a float4
 STEPS_PER_CHANNEL = 2311 * 3
 PROFILE_ROUND = 'r06'
 REFERENCE_CPU_FILE = os.path.join(ROOT, 'profiles', PROFILE_ROUND + '_reference_cpu.json')   # written by tools/time_reference_cpu.py
+DUMP_BYTES = 64 << 20              # --dump-outputs: at most 64 MiB in all
 
 
 def reference_cpu_record():
@@ -52,6 +58,32 @@ def reference_cpu_record():
         return rec
     except (OSError, ValueError):
         return None
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array of `arrays` (name -> numpy array) as out_dir/<name>.npy in float32."""
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise SystemExit('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
+def ald_outputs(alds):
+    """What a caller of the timed path holds after its last step: the channel estimates X [T, Nt, Nr] (real and imaginary
+    parts as a last axis of 2) and the NMSE that step logged per trajectory [T], in trajectory order.  Where they exceed
+    DUMP_BYTES: the same fixed, seeded sample of trajectories (in ascending order) for both."""
+    import torch
+    X = torch.cat([a.X for a in alds])
+    nmse = torch.cat([a.nmse_log()[a.steps_done() - 1] for a in alds])
+    per_traj = X[0].numel() * 8 + 4
+    if X.shape[0] * per_traj > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(X.shape[0], DUMP_BYTES // per_traj, replace=False))
+        sel = torch.from_numpy(keep).to(X.device)
+        X, nmse = X[sel], nmse[sel]
+    return {'channel_estimate': torch.view_as_real(X).cpu().numpy(), 'nmse': nmse.cpu().numpy()}
 
 
 def _cpu_worker(job):
@@ -139,8 +171,13 @@ def parse_args():
                     help='1: replay each step as a hipGraph, 0: eager launches; default: what the CLIs default to '
                          '(driver.DEFAULT_USE_GRAPH)')
     ap.add_argument('--full-schedule', action='store_true', help='time all 6933 steps instead of --steps')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run every other measurement: sustained segment, other launch mode, per-kernel '
+                         'roofline, exact mode, strong scaling, CPU baseline (the --no-* options and --sustained select among them)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path computed in its last step as DIR/<name>.npy (float32, at most 64 MiB)')
     ap.add_argument('--sustained', type=int, default=None,
-                    help='steps of the sustained segment timed after the K-step window (default 1000; 0 disables)')
+                    help='with --full: steps of the sustained segment timed after the K-step window (default 1000; 0 disables)')
     ap.add_argument('--no-strong', action='store_true', help='skip the strong-scaling (tuner grid) measurement')
     ap.add_argument('--no-other-mode', action='store_true', help='skip timing the non-default launch mode')
     ap.add_argument('--no-cpu-baseline', action='store_true')
@@ -169,7 +206,10 @@ def parse_args():
     ap.add_argument('--skip-spec', default=None,
                     help='JSON list of [branch prefix, anchor record prefix, lane] (plan.hoist_skip_branches) for the small-batch plan; '
                          '"0" = no launch lanes; default: plan.DEFAULT_SKIP_SPEC for batches of at most scorenet.SKIP_OVERLAP_MAX_T trajectories')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def bench_train(args):
@@ -203,11 +243,12 @@ def bench_train(args):
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
         loss = float(net.loss_per_sample.mean().item())
-        prof = net.profile_step(x, labels[0], repeats=3)
+        if args.dump_outputs:
+            # the last step's per-sample losses and the parameters it updated (flat, in the library's parameter layout)
+            write_outputs(args.dump_outputs, {'loss_per_sample': net.loss_per_sample.cpu().numpy(),
+                                              'parameters': net.params.detach().cpu().numpy()})
+        prof = net.profile_step(x, labels[0], repeats=3) if args.full else None
     flops = 3 * P.count_conv_flops(net.plan) * B                 # forward + input-gradient + weight-gradient convolutions
-    names = {P.CONV: 'conv', P.CONV_WGRAD: 'conv_wgrad', P.GRAD_ADD: 'grad_add', P.INORM_BWD: 'inorm_bwd'}
-    classes = {('forward ' if t < 200 else 'reverse ') + names.get(t % 100, 'kind %d' % (t % 100)): round(ms, 3)
-               for t, (ms, n) in sorted(prof.items(), key=lambda kv: -kv[1][0])[:6]}
     out = {'metric': 'samples/s DSM training step (train_score.py), CDL-C Nt64xNr16', 'value': B / dt, 'unit': 'samples/s',
            'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt * 1e3, 'higher_is_better': True,
            'scaling': 'weak', 'vs_baseline': None,
@@ -221,14 +262,17 @@ def bench_train(args):
                         'note': 'algorithmic conv FLOPs of the step (3 x forward) against the fp32 MFMA peak, the pipe the weight '
                                 'gradients run on; forward and input-gradient convolutions run as exact 3-term bf16 splits on the '
                                 'bf16 pipe (peak / 6 x 36/16 Winograd = 943.7 TFLOP/s algorithmic), so this fraction is an upper bound '
-                                'on how busy either pipe is',
-                        'ms_by_operator_class': classes},
+                                'on how busy either pipe is'},
            'cpu_baseline': {'value': None, 'unit': 'samples/s', 'cores': 0, 'kind': 'none',
                             'reference_build_container': {'value': 32 / 0.295, 'unit': 'samples/s', 'cores': 8,
                                                           'what': 'the reference step itself (NCSNv2Deepest + autograd + Adam + EMAHelper, '
                                                                   'PyTorch CPU): 0.26-0.33 s per step of 32 in the build container'},
                             'note': 'there is no CPU port of the backward pass to time on this host (the oracle restates loss and '
                                     'optimiser only), so `value` is null'}}
+    if prof is not None:
+        names = {P.CONV: 'conv', P.CONV_WGRAD: 'conv_wgrad', P.GRAD_ADD: 'grad_add', P.INORM_BWD: 'inorm_bwd'}
+        out['roofline']['ms_by_operator_class'] = {('forward ' if t < 200 else 'reverse ') + names.get(t % 100, 'kind %d' % (t % 100)): round(ms, 3)
+                                                   for t, (ms, n) in sorted(prof.items(), key=lambda kv: -kv[1][0])[:6]}
     print(json.dumps(out))
 
 
@@ -241,7 +285,7 @@ def main():
 
     # CPU baseline first: its worker processes are spawned, which must happen before this process touches the GPU
     cpu_base = None
-    if int(os.environ.get('WORLD_SIZE', '1')) == 1 and not args.no_cpu_baseline and args.workload == 'cdlc':
+    if args.full and int(os.environ.get('WORLD_SIZE', '1')) == 1 and not args.no_cpu_baseline and args.workload == 'cdlc':
         cpu_base = cpu_baseline()
 
     import torch
@@ -393,11 +437,13 @@ def main():
     # headline: the launch mode and stream count the CLIs default to; nothing but the K steps inside the timed region
     dt = timed(alds, streams, K, use_graph, args.warmup)
     rank_times = per_rank(K)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, ald_outputs(alds))       # (before any later segment moves the estimates on)
     other = None
-    if not args.no_other_mode and not args.full_schedule:
+    if args.full and not args.no_other_mode and not args.full_schedule:
         other = timed(alds, streams, K, not use_graph, args.warmup)
     n_sus = (0 if args.full_schedule else 1000 if not big else 40) if args.sustained is None else args.sustained
-    n_sus = min(n_sus, STEPS_PER_CHANNEL - args.warmup)
+    n_sus = min(n_sus, STEPS_PER_CHANNEL - args.warmup) if args.full else 0
     dt_sus = timed(alds, streams, n_sus, use_graph, args.warmup) if n_sus > 0 else None
 
     # the one collective of the path: gather the per-step mean NMSE curves of every rank (RCCL over xGMI)
@@ -420,7 +466,7 @@ def main():
     # is what a per-kernel roofline means and what `rocprofv3 --kernel-trace --stats` of a one-stream run reports); each tagged
     # kernel class is bracketed by hipEvents on the launch stream (sbc_plan_profile) in its own short segment.
     klass = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         p_alds, p_streams = make_batches(H, Pm, idx, idx, ln, np.full(T, 3e-11), np.full(T, 0.01), rank * T + np.arange(T), init, 1)
         pa = p_alds[0]
         run_all(p_alds, p_streams, 2, False)
@@ -459,7 +505,7 @@ def main():
 
     # ---------------------------------------------------------------- the same steps in the exact mode (bf16x3), for comparison
     exact = None
-    if conv_mode == 'f16x2' and not args.no_exact_mode and not args.full_schedule and not big:
+    if args.full and conv_mode == 'f16x2' and not args.no_exact_mode and not args.full_schedule and not big:
         net_f16x2 = net
         net = net_f16x2.fallback_net()                    # same checkpoint, conv_mode bf16x3 (what a flagged batch is re-run with)
         e_alds, e_streams = make_batches(H, Pm, idx, idx, ln, np.full(T, 3e-11), np.full(T, 0.01), rank * T + np.arange(T), init,
@@ -478,7 +524,7 @@ def main():
 
     # ---------------------------------------------------------------- strong workload: the tuner grid, sharded
     strong = None
-    if not args.no_strong and not big and not args.full_schedule:
+    if args.full and not args.no_strong and not big and not args.full_schedule:
         cells = [(a, b) for a in (3e-11, 6e-11, 1e-10, 3e-10) for b in (0.1, 0.01, 0.001)]     # tune_hparams_score.py:20-23
         nC, nS, nB = len(cells), 17, 100
         Ttot = nC * nS * nB
@@ -511,7 +557,7 @@ def main():
     # only strong-scaling evidence a one-GPU box can give for BASELINE configs[1] -- an upper bound on the 2/4/8-GPU rate of that
     # workload (the final gather is a few ms once per run), not a measured scaling curve
     strong_small = None
-    if world == 1 and not args.no_strong and not big and not args.full_schedule:
+    if args.full and world == 1 and not args.no_strong and not big and not args.full_schedule:
         strong_small = {'what': 'ms per Langevin step of rank 0\'s block when the %d trajectories of the default test_score run '
                                 '(BASELINE configs[1]) are sharded over W ranks (shard.my_block), timed on this ONE GPU with the CLI '
                                 'defaults (blocks of at most scorenet.SKIP_OVERLAP_MAX_T trajectories: one batch, skip branches on a launch lane); '
@@ -538,7 +584,7 @@ def main():
     # job -- the 1700 trajectories of one default test_score run, shard.my_block per rank, barrier + max over ranks like the headline: a
     # MEASUREMENT of what `torchrun ... test_score` does with its trajectories on N GPUs (the weak line above gives every rank its own 1700)
     strong_cfg2 = None
-    if world > 1 and not args.no_strong and not big and not args.full_schedule:
+    if args.full and world > 1 and not args.no_strong and not big and not args.full_schedule:
         lo, hi = shard.my_block(T, rank, world)
         sel = np.arange(lo, hi)
         q_alds, q_streams = make_batches(H, Pm, idx[sel], idx[sel], ln[sel], np.full(len(sel), 3e-11), np.full(len(sel), 0.01), sel, init, n_streams)
@@ -611,7 +657,8 @@ def main():
             out['exact_mode'] = exact
             out['config']['exact_mode_bf16x3_channels_per_s'] = round(exact['value'], 3)
         out['per_rank'] = rank_times
-        out['config']['one_stream_ms_per_step'] = one_stream_ms
+        if args.full:
+            out['config']['one_stream_ms_per_step'] = one_stream_ms
         if conv_mode == 'f16x2':
             out['config']['f16x2_range_flag'] = int(range_flag)          # 0: every staged activation stayed inside the fp16 range
         if klass:

@@ -1,10 +1,11 @@
-"""bench.py keeps the driver's contract: one JSON line with the headline keys, the roofline and (N = 1) cpu_baseline objects,
-and it starts its own ranks for --gpus N.  Short runs on the GPU box (``pytest -m gpu``)."""
+"""bench.py keeps the driver's contract: one JSON line with the headline keys (with --full also the roofline and (N = 1)
+cpu_baseline objects), --dump-outputs, and it starts its own ranks for --gpus N.  Short runs on the GPU box (``pytest -m gpu``)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -25,7 +26,7 @@ def _run(*args):
 
 
 def test_bench_line_contract_single_gpu():
-    d = _run('--steps', '4', '--warmup', '1', '--channels', '8', '--snr-points', '4', '--sustained', '6', '--no-cpu-baseline')
+    d = _run('--full', '--steps', '4', '--warmup', '1', '--channels', '8', '--snr-points', '4', '--sustained', '6', '--no-cpu-baseline')
     assert KEYS <= set(d) and d['n_gpus'] == 1 and d['steps'] == 4 and d['scaling'] == 'weak' and d['vs_baseline'] is None
     assert d['value'] > 0 and abs(d['value'] - 32 / (6933 * d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
     assert 'workload' in d['config'] and 'model' not in d['config'] and d['config']['nmse_finite']
@@ -48,6 +49,21 @@ def test_bench_line_contract_single_gpu():
     assert d['config']['rank_share_ms_per_step_T16'] > 0 and d['config']['exact_mode_bf16x3_channels_per_s'] > 0 and d['config']['sustained_channels_per_s'] > 0
 
 
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line holds the headline and nothing that takes runs of its own; --steps is the number of timed steps.
+    --dump-outputs writes the channel estimates and NMSE of the last timed step, the same from run to run (seeded inputs)."""
+    args = ('--steps', '3', '--warmup', '1', '--channels', '8', '--snr-points', '4')
+    d = _run(*args, '--dump-outputs', str(tmp_path / 'a'))
+    assert KEYS - {'roofline'} <= set(d) and d['steps'] == 3 and d['warmup'] == 1 and d['config']['nmse_finite']
+    assert abs(d['value'] - 32 / (6933 * d['ms_per_step'] * 1e-3)) < 1e-6 * d['value'] and d['dtype'].startswith('f16x2')
+    assert not {'roofline', 'cpu_baseline', 'strong', 'strong_small', 'exact_mode', 'other_launch_mode', 'sustained_steps'} & set(d)
+    _run(*args, '--dump-outputs', str(tmp_path / 'b'))
+    for name, shape in (('channel_estimate', (32, 64, 16, 2)), ('nmse', (32,))):
+        a, b = np.load(str(tmp_path / 'a' / (name + '.npy'))), np.load(str(tmp_path / 'b' / (name + '.npy')))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all() and np.array_equal(a, b)
+    assert (np.load(str(tmp_path / 'a' / 'nmse.npy')) > 0).all()
+
+
 def test_bench_self_launches_its_ranks():
     """``python bench.py --gpus 2`` with no torchrun environment: the parent starts the ranks as children and rank 0 prints the
     line with the aggregate over both.  On this one-GPU box two ranks must share the device, which bench.py only accepts when it
@@ -61,7 +77,7 @@ def test_bench_self_launches_its_ranks():
                              capture_output=True, text=True, timeout=900, env=env_clean)
         assert bad.returncode != 0 and 'one rank per GPU' in (bad.stderr + bad.stdout)
         env_clean['SBC_DIST_BACKEND'] = 'gloo'
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '2', '--steps', '3', '--warmup', '1',
                         '--channels', '8', '--snr-points', '4', '--sustained', '0', '--no-other-mode'],
                        capture_output=True, text=True, timeout=900, env=env_clean)
     assert p.returncode == 0, p.stderr[-2000:]

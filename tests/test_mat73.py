@@ -1,7 +1,7 @@
 """MATLAB ``-v7.3`` (HDF5) reading without an HDF5 library (reference ``loaders.py:23-33``).
 
-Fixtures: files written by the REAL HDF5 library in MATLAB's layout (tests/gen_mat_fixture.py, build container), and --
-when scipy's test data is installed -- a file written by MATLAB 7.4 itself."""
+Fixtures: files written by the REAL HDF5 library in MATLAB's layout (tests/gen_mat_fixture.py, build container), and a file
+written by MATLAB 7.4 itself (from scipy's test data, stored under tests/golden/)."""
 import os
 import shutil
 
@@ -41,11 +41,9 @@ def test_layout_and_type_variants(name):
 
 
 def test_file_written_by_matlab_itself():
-    """scipy ships a v7.3 file saved by MATLAB 7.4 (HDF5 1.6-era layout message) next to the same variable in v7 format."""
-    d = os.path.join(os.path.dirname(__import__('scipy.io').io.__file__), 'matlab', 'tests', 'data')
-    f73, f7 = os.path.join(d, 'testhdf5_7.4_GLNX86.mat'), os.path.join(d, 'testdouble_7.4_GLNX86.mat')
-    if not (os.path.exists(f73) and os.path.exists(f7)):
-        pytest.skip('scipy test data not installed')
+    """A v7.3 file saved by MATLAB 7.4 (HDF5 1.6-era layout message) next to the same variable in v7 format (both from scipy's
+    test data)."""
+    f73, f7 = os.path.join(GOLDEN, 'testhdf5_7.4_GLNX86.mat'), os.path.join(GOLDEN, 'testdouble_7.4_GLNX86.mat')
     import scipy.io
     assert mat73.list_variables(f73) == ['testdouble']
     assert np.array_equal(mat73.loadmat_variable(f73, 'testdouble'), scipy.io.loadmat(f7)['testdouble'])

@@ -9,8 +9,9 @@ import torch.multiprocessing as mp
 
 
 def _worker(rank, world, port, n_items, n_steps, q):
+    # (SBC_DIST_BACKEND=gloo: on a box with fewer GPUs than ranks, the ranks share a device on purpose -- shard.init_distributed)
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      LOCAL_RANK=str(rank))
+                      LOCAL_RANK=str(rank), SBC_DIST_BACKEND='gloo')
     from score_based_channels_amd import shard
     r, w, _ = shard.init_distributed('gloo')
     assert (r, w) == (rank, world)
@@ -43,7 +44,7 @@ def _failing_worker(rank, world, port, q):
     all_gather until the process-group timeout.  Also: the fallback records of every rank reach every rank (gather_objects)."""
     import time
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      LOCAL_RANK=str(rank))
+                      LOCAL_RANK=str(rank), SBC_DIST_BACKEND='gloo')
     from score_based_channels_amd import shard
     r, w, _ = shard.init_distributed('gloo')
     t0 = time.time()
@@ -86,7 +87,7 @@ def _late_failing_worker(rank, world, port, q):
     collective nobody matches: it returns at once, and the healthy rank -- which has no agreement point left -- finishes normally."""
     import time
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      LOCAL_RANK=str(rank), SBC_DIST_TIMEOUT_S='60')
+                      LOCAL_RANK=str(rank), SBC_DIST_TIMEOUT_S='60', SBC_DIST_BACKEND='gloo')
     from score_based_channels_amd import shard
     r, w, _ = shard.init_distributed('gloo')
     t0 = time.time()

@@ -16,7 +16,7 @@ CANDIDATES = (['conv_x3_kernel<32, 32, 3, 2, 1, 4, 1, true, 1>', 'conv_wx3_kerne
                'conv_chain_kernel<64, 4, 4, 1>', 'conv_chain_kernel<64, 8, 8, 1>', 'conv_chain_kernel<32, 8, 4, 1>'])
 PX = (256 * 64) if BIG else (64 * 16)
 T = 1024 if BIG else 1700
-CMD = '--workload %s --streams 1 --no-cpu-baseline --no-strong --no-other-mode --no-exact-mode --sustained 0' % W
+CMD = '--full --workload %s --streams 1 --no-cpu-baseline --no-strong --no-other-mode --no-exact-mode --sustained 0' % W
 DESC = ('conv_mode f16w + fused RCU pairs + folded statistics, one stream, T=1024 (256x64 arrays)' if BIG else
         'conv_mode f16x2 (calibrated activation scales) + fused RCU pairs, CRP stages, ResidualBlocks and low-resolution chains + folded statistics, one stream, T=1700')
 

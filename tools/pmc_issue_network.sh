@@ -4,7 +4,7 @@
 # instruction, 16 per v_mfma_f32_16x16x32_f16 and per transcendental).
 R=$PWD; OUT=$R/gpurun_out/pmc_issue; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-ARGS="--steps 2 --warmup 1 --streams 1 --no-exact-mode --no-strong --no-other-mode --no-cpu-baseline --sustained 0"
+ARGS="--full --steps 2 --warmup 1 --streams 1 --no-exact-mode --no-strong --no-other-mode --no-cpu-baseline --sustained 0"
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_VALU_TRANS GRBM_GUI_ACTIVE SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM --output-format csv -d $OUT -o p -- python3 $R/bench.py $ARGS > $OUT/run.log 2>&1
 cd $R
 python3 - "$OUT" <<'PY'

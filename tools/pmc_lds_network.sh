@@ -2,7 +2,7 @@
 # LDS counters of every kernel of the one-stream Langevin step (GPU box): conflict share and LDS-array occupancy per kernel.
 R=$PWD; OUT=$R/gpurun_out/pmc_lds; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $OUT -o p -- python3 $R/bench.py --steps 2 --warmup 1 --streams 1 --no-exact-mode --no-strong --no-other-mode --no-cpu-baseline --sustained 0 > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $OUT -o p -- python3 $R/bench.py --full --steps 2 --warmup 1 --streams 1 --no-exact-mode --no-strong --no-other-mode --no-cpu-baseline --sustained 0 > $OUT/run.log 2>&1
 cd $R
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections
