@@ -536,6 +536,52 @@ int sbc_debug_complex_normal(uint64_t seed, int64_t traj, int32_t step, int32_t 
 /* scratch floats SBC_OP_CONV_WGRAD / END_CONV_BWD / BEGIN_CONV_BWD need in `aux` for this shape */
 int64_t sbc_wgrad_scratch_floats(int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t ksize);
 
+/* --- classical baselines (Fig. 5c of the paper): Lasso / fsAD and ML ----------------------------------------------------------
+ * Batched solvers of independent problems, one launch each, asynchronous on `stream`.  Complex data are interleaved float32
+ * (re, im); pointers are device pointers.  A problem's arithmetic does not depend on its position in the batch or on B.
+ *
+ * sbc_l1_lifted_run: `steps` iterations of accelerated proximal gradient (sigpy.alg.GradientMethod, accelerate=True, proxg =
+ * sigpy.prox.L1Reg(lambda)) on the lifted-DFT l1 problem of src/score_based_channels/test_l1Fourier_lifted.py:125-190, for every
+ * problem b of the batch:
+ *     Ld = conj(ifft(eye(Nt), n=L Nt, norm='ortho'))  [Nt][n1],  Rd = ifft(eye(Nr), n=L Nr, norm='ortho').T  [n2][Nr]   (:125-130)
+ *     f(X) = 1/2 ||P Ld X Rd - Y||^2;  x = z = 0, t = 1;  per step  x_old = x;  x = soft(lambda lr, z - lr grad f(z));
+ *     t' = (1 + sqrt(1 + 4 t^2)) / 2;  z = x + (t - 1) / t' (x - x_old);  t = t'                                       (:145-166)
+ *     nmse[k][b] = ||Ld x Rd - H||^2 / ||H||^2 of the new x                                                              (:168-178)
+ * soft(tau, v) = max(|v| - tau, 0) v / |v| (0 where v = 0).  Nothing is clamped: a step size above 1 / ||P||^2 diverges to
+ * inf / NaN as the reference does.  Supported: Nt = 64, Nr = 16, 1 <= Np <= Nt, lifting L in {1, 2, 4} (n1 = L Nt, n2 = L Nr);
+ * other shapes return SBC_ERR_UNSUPPORTED.  A p_index / h_index entry outside [0, nP) / [0, nH) gives a NaN log for that problem. */
+typedef struct sbc_l1_lifted_desc {
+    const float* P;            /* [nP][Np][Nt] pilots, val_P of :112-113                                                       */
+    const int32_t* p_index;    /* [B] pilot matrix of problem b, or NULL = b                                                   */
+    const float* Y;            /* [B][Np][Nr] measurements, val_Y of :137-140                                                   */
+    const float* Htrue;        /* [nH][Nt][Nr] channels, val_H of :114-115 (the NMSE reference)                                 */
+    const int32_t* h_index;    /* [B] channel of problem b, or NULL = b                                                        */
+    const float* lmbda;        /* [B] l1 weight (L1Reg lamda, :133)                                                             */
+    const float* lr;           /* [B] step size (GradientMethod alpha, :159-161)                                                */
+    float* nmse;               /* [steps][B] float32 per-step NMSE log (complete_log, :172-178)                                 */
+    float* H_hat;              /* [B][Nt][Nr] final Ld x Rd (:181), or NULL                                                     */
+    float* X;                  /* [B][n1][n2] final x (val_H_hat), or NULL                                                      */
+    int32_t B, nP, nH, Nt, Nr, Np, lifting, steps;
+} sbc_l1_lifted_desc;
+int sbc_l1_lifted_run(const sbc_l1_lifted_desc* desc, void* stream);
+
+/* sbc_ls_regularized: per problem b, H_hat = (P^H P + s2 I_Nt)^-1 P^H Y with s2 = noise_var[b] (src/score_based_channels/
+ * test_ml.py:132-138, there 10^(-SNR/10), no Nt factor), solved as the equivalent system of size min(Np, Nt) -- for Np <= Nt
+ * H_hat = P^H (P P^H + s2 I_Np)^-1 Y -- by an fp32 Cholesky factorisation; and nmse[b] = ||H_hat - H||^2 / ||H||^2 (:141-145).
+ * noise_var must be > 0 (not checked on the device).  Supported: min(Np, Nt) <= 64, Nr <= 64, Nt, Np <= 1024. */
+typedef struct sbc_ls_desc {
+    const float* P;            /* [nP][Np][Nt] pilots (val_P, :109-111)                                                        */
+    const int32_t* p_index;    /* [B] or NULL = b                                                                              */
+    const float* Y;            /* [B][Np][Nr] measurements (val_Y, :125-129)                                                    */
+    const float* noise_var;    /* [B] s2 (local_noise, :135)                                                                   */
+    const float* Htrue;        /* [nH][Nt][Nr] channels, or NULL (then nmse must be NULL)                                      */
+    const int32_t* h_index;    /* [B] or NULL = b                                                                              */
+    float* H_hat;              /* [B][Nt][Nr] estimate (est_H, :138)                                                           */
+    float* nmse;               /* [B] or NULL (oracle_log, :141-145)                                                           */
+    int32_t B, nP, nH, Nt, Nr, Np;
+} sbc_ls_desc;
+int sbc_ls_regularized(const sbc_ls_desc* desc, void* stream);
+
 /* ---- Environment variables -------------------------------------------------------------------------------------------------
  * Everything the library (csrc/) and the Python host (score_based_channels_amd/) read from the environment, in ONE place.  None of them
  * changes a result: they select between launch plans / kernel variants that compute the same sums (A/B timing aids, each verified

@@ -18,7 +18,7 @@ EXPORTS = ('sbc_abi_version', 'sbc_set_persistent_cus', 'sbc_last_error', 'sbc_d
            'sbc_pack_conv_weight_f16x2', 'sbc_pack_conv_weight_winograd_f16x2', 'sbc_pack_conv_weight_pooled_f16x2', 'sbc_range_flag',
            'sbc_f16x2_calibration_input', 'sbc_f16x2_calibrate', 'sbc_debug_philox4x32', 'sbc_debug_complex_normal',
            'sbc_score_create', 'sbc_score_buffers', 'sbc_score_ops', 'sbc_score_level_source', 'sbc_score_forward',
-           'sbc_score_destroy', 'sbc_wgrad_scratch_floats')
+           'sbc_score_destroy', 'sbc_wgrad_scratch_floats', 'sbc_l1_lifted_run', 'sbc_ls_regularized')
 
 
 class SbcError(RuntimeError):
@@ -83,6 +83,20 @@ class sbc_score_desc(C.Structure):
                 ('conv_mode', C.c_int32), ('sigmas', C.c_void_p), ('num_classes', C.c_int32), ('flags', C.c_int32)]
 
 
+# classical baselines (baselines.py): lifted-DFT l1 (Lasso / fsAD) and regularised least squares (ML)
+class sbc_l1_lifted_desc(C.Structure):
+    _fields_ = [('P', C.c_void_p), ('p_index', C.c_void_p), ('Y', C.c_void_p), ('Htrue', C.c_void_p), ('h_index', C.c_void_p),
+                ('lmbda', C.c_void_p), ('lr', C.c_void_p), ('nmse', C.c_void_p), ('H_hat', C.c_void_p), ('X', C.c_void_p),
+                ('B', C.c_int32), ('nP', C.c_int32), ('nH', C.c_int32), ('Nt', C.c_int32), ('Nr', C.c_int32), ('Np', C.c_int32),
+                ('lifting', C.c_int32), ('steps', C.c_int32)]
+
+
+class sbc_ls_desc(C.Structure):
+    _fields_ = [('P', C.c_void_p), ('p_index', C.c_void_p), ('Y', C.c_void_p), ('noise_var', C.c_void_p), ('Htrue', C.c_void_p),
+                ('h_index', C.c_void_p), ('H_hat', C.c_void_p), ('nmse', C.c_void_p),
+                ('B', C.c_int32), ('nP', C.c_int32), ('nH', C.c_int32), ('Nt', C.c_int32), ('Nr', C.c_int32), ('Np', C.c_int32)]
+
+
 _lib = None
 
 
@@ -129,6 +143,8 @@ def lib():
     h.sbc_score_destroy.restype = None
     h.sbc_wgrad_scratch_floats.argtypes = [C.c_int32] * 6
     h.sbc_wgrad_scratch_floats.restype = C.c_int64
+    h.sbc_l1_lifted_run.argtypes = [C.POINTER(sbc_l1_lifted_desc), C.c_void_p]
+    h.sbc_ls_regularized.argtypes = [C.POINTER(sbc_ls_desc), C.c_void_p]
     if h.sbc_abi_version() != ABI_VERSION:
         raise SbcError('libsbc_hip.so ABI %d != expected %d' % (h.sbc_abi_version(), ABI_VERSION))
     _lib = h

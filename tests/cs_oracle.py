@@ -1,0 +1,198 @@
+"""numpy oracles of the classical baselines (Fig. 5c): restatements of the reference scripts with their solvers written out.
+
+* ``l1_run``: ``src/score_based_channels/test_l1Fourier_lifted.py:125-190`` -- sigpy's ``GradientMethod(accelerate=True)`` with
+  ``L1Reg`` -- using sigpy's operator algebra literally: the dictionaries built with ``scipy.fft.ifft`` as in :125-128,
+  ``array_op = Compose((MatMul(Ld), RightMatMul(Rd)))`` = ``x -> Ld @ (x @ Rd)``, ``fw_op = Compose((MatMul(P), array_op))`` and
+  ``fw_op.H`` = ``r -> (Ld^H @ (P^H @ r)) @ Rd^H``.  Batched over problems; float64 by default, complex64 on request.
+* ``lstsq_run``: the ``np.linalg.lstsq`` loop of ``test_ml.py:124-145``.
+* ``l1_script`` / ``ml_script``: the two scripts' main loops (test_l1Fourier_lifted.py:45-211, test_ml.py:45-154) on the package's
+  loader (synthetic channels) with numpy's legacy global RNG seeded once, the solvers replaced by the restatements above -- the
+  precedent of ``gen_golden.reference_ald``.
+"""
+import copy
+import itertools
+
+import numpy as np
+from scipy.fft import ifft
+
+from score_based_channels_amd.config import Config, default_config
+from score_based_channels_amd.loaders import Channels
+
+
+def dictionaries(nt, nr, lifting):
+    """(Ld [Nt, L Nt], Rd [L Nr, Nr]) exactly as test_l1Fourier_lifted.py:125-128."""
+    left = np.conj(ifft(np.eye(nt), n=nt * lifting, norm='ortho'))
+    right = ifft(np.eye(nr), n=nr * lifting, norm='ortho').T
+    return left, right
+
+
+def array_op(Ld, Rd, x):
+    return Ld @ (x @ Rd)
+
+
+def array_op_H(Ld, Rd, y):
+    return (np.conj(Ld.T) @ y) @ np.conj(Rd.T)
+
+
+def fw_op(P, Ld, Rd, x):
+    return P @ array_op(Ld, Rd, x)
+
+
+def fw_op_H(P, Ld, Rd, r):
+    return array_op_H(Ld, Rd, np.conj(np.swapaxes(P, -1, -2)) @ r)
+
+
+def soft_thresh(lamda, x):
+    """sigpy.util.soft_thresh."""
+    a = np.abs(x)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        sign = np.where(a > 0, x / a, 0)
+    mag = a - lamda
+    mag = (np.abs(mag) + mag) / 2
+    return mag * sign
+
+
+def t_sequence(steps):
+    """(t_k, c_k = (t_k - 1) / t_{k+1}) of the accelerated method, t_0 = 1."""
+    t, ts, cs = 1.0, [], []
+    for _ in range(steps):
+        tn = (1 + (1 + 4 * t ** 2) ** 0.5) / 2
+        ts.append(t)
+        cs.append((t - 1) / tn)
+        t = tn
+    return np.asarray(ts), np.asarray(cs)
+
+
+def l1_run(P, Y, H, lmbda, lr, lifting=4, steps=1000, dtype=np.complex128):
+    """Batched restatement of :145-189.  ``P`` [B, Np, Nt], ``Y`` [B, Np, Nr], ``H`` [B, Nt, Nr]; ``lmbda`` / ``lr`` scalars or [B].
+    Returns (log [steps, B] float64, H_hat [B, Nt, Nr], X [B, L Nt, L Nr])."""
+    rdt = np.float32 if dtype == np.complex64 else np.float64
+    P, Y, H = (np.asarray(a).astype(dtype) for a in (P, Y, H))
+    B, _, nt = P.shape
+    nr = Y.shape[2]
+    Ld, Rd = (m.astype(dtype) for m in dictionaries(nt, nr, lifting))
+    lam = np.broadcast_to(np.asarray(lmbda, np.float64), (B,))[:, None, None]
+    lrs = np.broadcast_to(np.asarray(lr, np.float64), (B,))[:, None, None]
+    tau, lrs = (lam * lrs).astype(rdt), lrs.astype(rdt)
+    x = np.zeros((B, nt * lifting, nr * lifting), dtype)
+    z = x.copy()
+    t = 1.0
+    hn = np.sum(np.abs(H.astype(np.complex128)) ** 2, axis=(-1, -2))
+    log = np.empty((steps, B))
+    est = None
+    for k in range(steps):
+        x_old = x
+        g = fw_op_H(P, Ld, Rd, fw_op(P, Ld, Rd, z) - Y)          # gradf(x) = fw_op.H * (fw_op * x - y), at x = z
+        x = soft_thresh(tau, z - lrs * g)                          # axpy(x, -alpha, gradf(x)); proxg(alpha, x)
+        t_old = t
+        t = (1 + (1 + 4 * t_old ** 2) ** 0.5) / 2
+        z = x + dtype((t_old - 1) / t) * (x - x_old)
+        est = array_op(Ld, Rd, x)
+        log[k] = np.sum(np.abs((est - H).astype(np.complex128)) ** 2, axis=(-1, -2)) / hn
+    return log, est, x
+
+
+def lstsq_run(P, Y, H, noise):
+    """test_ml.py:131-145 per problem: lstsq of (P^H P + noise I) H = P^H Y.  Returns (H_hat [B, Nt, Nr], nmse [B])."""
+    B, _, nt = P.shape
+    noise = np.broadcast_to(np.asarray(noise, np.float64), (B,))
+    est = np.empty((B, nt, Y.shape[2]), np.complex128)
+    nmse = np.empty(B)
+    for b in range(B):
+        normal_P = np.matmul(P[b].T.conj(), P[b]) + noise[b] * np.eye(nt)
+        normal_Y = np.matmul(P[b].T.conj(), Y[b])
+        est[b] = np.linalg.lstsq(normal_P, normal_Y, rcond=None)[0]
+        nmse[b] = np.sum(np.abs(est[b] - H[b]) ** 2) / np.sum(np.abs(H[b]) ** 2)
+    return est, nmse
+
+
+def _validation_set(val_seed, val_config, norm, kept, synthetic):
+    """:104-122 -- the whole validation set read in ONE DataLoader batch (every item's draws), then sliced."""
+    val_dataset = Channels(val_seed, val_config, norm=norm, synthetic=synthetic)
+    items = [val_dataset[i] for i in range(len(val_dataset))]
+    P = np.stack([it['P'] for it in items])
+    Hh = np.stack([it['H_herm'] for it in items])
+    val_P = np.conj(np.swapaxes(P, -1, -2))[:kept]
+    val_H = (Hh[:, 0] + 1j * Hh[:, 1]).astype(np.complex64)[:kept]
+    return val_P, val_H
+
+
+def l1_script(train='CDL-C', test='CDL-C', antennas=(16, 64), array='ULA', spacing=0.5, alpha=(0.6,), lmbda=(0.3,), lifting=4,
+              steps=1000, lr=(3e-3,), seed=1, kept_samples=50, synthetic=True, solve=l1_run):
+    """test_l1Fourier_lifted.py:45-211 with ``solve`` in place of sigpy.  Returns the dict the script saves (without config / args)."""
+    np.random.seed(seed)
+    config = Config()
+    config.data.channel = train
+    config.data.array = array
+    config.data.image_size = [antennas[0], antennas[1]]
+    config.data.num_pilots = antennas[1]
+    config.data.spacing_list = [spacing]
+    config.data.noise_std = 1
+    config.data.mixed_channels = False
+    train_seed, val_seed = 1234, 4321
+    dataset = Channels(train_seed, config, norm='global', synthetic=synthetic)
+    snr_range = np.asarray(np.arange(-10, 35, 5))
+    spacing_range, alpha_range = np.asarray([spacing]), np.asarray(alpha)
+    lmbda_range, lr_range = np.asarray(lmbda), np.asarray(lr)
+    noise_range = 10 ** (-snr_range / 10.) * antennas[1]
+    shape = (len(spacing_range), len(alpha_range), len(lmbda_range), len(lr_range))
+    nmse_log = np.zeros(shape + (len(snr_range), kept_samples))
+    complete_log = np.zeros(shape + (len(snr_range), steps, kept_samples))
+    for meta_idx, (sp, al, lm, lrv) in enumerate(itertools.product(spacing_range, alpha_range, lmbda_range, lr_range)):
+        si, ai, li, ri = np.unravel_index(meta_idx, shape)
+        val_config = copy.deepcopy(config)
+        val_config.data.channel = test
+        val_config.data.spacing_list = [sp]
+        val_config.data.num_pilots = int(np.floor(antennas[1] * al))
+        val_P, val_H = _validation_set(val_seed, val_config, [dataset.mean, dataset.std], kept_samples, synthetic)
+        for snr_idx, local_noise in enumerate(noise_range):
+            val_Y = np.matmul(val_P, val_H)
+            val_Y = val_Y + np.sqrt(local_noise) / np.sqrt(2.) * (np.random.normal(size=val_Y.shape) +
+                                                                  1j * np.random.normal(size=val_Y.shape))
+            log, _, _ = solve(val_P, val_Y, val_H, lm, lrv, lifting, steps)
+            complete_log[si, ai, li, ri, snr_idx] = log
+            nmse_log[si, ai, li, ri, snr_idx] = log[-1]
+    avg_nmse = np.mean(nmse_log, axis=-1)
+    best_nmse = np.zeros((len(alpha_range), len(snr_range)))
+    best_lmbda, best_lr = np.zeros_like(best_nmse), np.zeros_like(best_nmse)
+    for ai in range(len(alpha_range)):
+        for snr_idx in range(len(snr_range)):
+            local = avg_nmse[0, ai, ..., snr_idx].flatten()
+            best = np.argmin(local)
+            li, ri = np.unravel_index(best, (len(lmbda_range), len(lr_range)))
+            best_nmse[ai, snr_idx], best_lmbda[ai, snr_idx], best_lr[ai, snr_idx] = local[best], lmbda_range[li], lr_range[ri]
+    return {'complete_log': complete_log, 'nmse_log': nmse_log, 'best_nmse': best_nmse, 'best_lmbda': best_lmbda,
+            'best_lr': best_lr, 'snr_range': snr_range, 'spacing_range': spacing_range, 'alpha_range': alpha_range,
+            'lmbda_range': lmbda_range, 'lr_range': lr_range}
+
+
+def ml_script(model='CDL-D', channel='CDL-D', antennas=(16, 64), array='ULA', spacing=(0.5,), alpha=(0.6,), seed=1,
+              kept_samples=50, synthetic=True):
+    """test_ml.py:45-154 (config from ``default_config(model)``, the checkpoint of :46-48 not being available)."""
+    np.random.seed(seed)
+    config = default_config(model, image_size=antennas)
+    config.sampling.sigma = 0.
+    config.data.channel = model
+    config.data.array = array
+    config.data.image_size = [antennas[0], antennas[1]]
+    config.data.spacing_list = [spacing[0]]
+    train_seed, val_seed = 1234, 4321
+    dataset = Channels(train_seed, config, norm=config.data.norm_channels, synthetic=synthetic)
+    snr_range = np.asarray(np.arange(-30, 17.5, 2.5))
+    spacing_range, alpha_range = np.asarray(spacing), np.asarray(alpha)
+    noise_range = 10 ** (-snr_range / 10.)
+    oracle_log = np.zeros((len(spacing_range), len(alpha_range), len(snr_range), kept_samples))
+    for meta_idx, (sp, al) in enumerate(itertools.product(spacing_range, alpha_range)):
+        si, ai = np.unravel_index(meta_idx, (len(spacing_range), len(alpha_range)))
+        val_config = copy.deepcopy(config)
+        val_config.purpose = 'val'
+        val_config.data.channel = channel
+        val_config.data.spacing_list = [sp]
+        val_config.data.num_pilots = int(np.floor(antennas[1] * al))
+        val_P, val_H = _validation_set(val_seed, val_config, [dataset.mean, dataset.std], kept_samples, synthetic)
+        for snr_idx, local_noise in enumerate(noise_range):
+            val_Y = np.matmul(val_P, val_H)
+            val_Y = val_Y + np.sqrt(local_noise) / np.sqrt(2.) * (np.random.normal(size=val_Y.shape) +
+                                                                  1j * np.random.normal(size=val_Y.shape))
+            _, oracle_log[si, ai, snr_idx] = lstsq_run(val_P, val_Y, val_H, local_noise)
+    return {'snr_range': snr_range, 'spacing_range': spacing_range, 'alpha_range': alpha_range, 'oracle_log': oracle_log}
