@@ -549,7 +549,9 @@ int64_t sbc_wgrad_scratch_floats(int32_t B, int32_t H, int32_t W, int32_t cin, i
  *     nmse[k][b] = ||Ld x Rd - H||^2 / ||H||^2 of the new x                                                              (:168-178)
  * soft(tau, v) = max(|v| - tau, 0) v / |v| (0 where v = 0).  Nothing is clamped: a step size above 1 / ||P||^2 diverges to
  * inf / NaN as the reference does.  Supported: Nt = 64, Nr = 16, 1 <= Np <= Nt, lifting L in {1, 2, 4} (n1 = L Nt, n2 = L Nr);
- * other shapes return SBC_ERR_UNSUPPORTED.  A p_index / h_index entry outside [0, nP) / [0, nH) gives a NaN log for that problem. */
+ * other shapes return SBC_ERR_UNSUPPORTED.  A p_index / h_index entry outside [0, nP) / [0, nH) gives a NaN log for that problem
+ * and fills its H_hat and X (where given) with NaN; nothing is read through the bad index and no other problem is affected.
+ * A refused call (any status but SBC_OK) has written nothing; B = 0 is SBC_OK and launches nothing. */
 typedef struct sbc_l1_lifted_desc {
     const float* P;            /* [nP][Np][Nt] pilots, val_P of :112-113                                                       */
     const int32_t* p_index;    /* [B] pilot matrix of problem b, or NULL = b                                                   */
@@ -568,7 +570,10 @@ int sbc_l1_lifted_run(const sbc_l1_lifted_desc* desc, void* stream);
 /* sbc_ls_regularized: per problem b, H_hat = (P^H P + s2 I_Nt)^-1 P^H Y with s2 = noise_var[b] (src/score_based_channels/
  * test_ml.py:132-138, there 10^(-SNR/10), no Nt factor), solved as the equivalent system of size min(Np, Nt) -- for Np <= Nt
  * H_hat = P^H (P P^H + s2 I_Np)^-1 Y -- by an fp32 Cholesky factorisation; and nmse[b] = ||H_hat - H||^2 / ||H||^2 (:141-145).
- * noise_var must be > 0 (not checked on the device).  Supported: min(Np, Nt) <= 64, Nr <= 64, Nt, Np <= 1024. */
+ * noise_var must be > 0 (not checked on the device).  Supported: min(Np, Nt) <= 64, Nr <= 64, Nt, Np <= 1024; other shapes return
+ * SBC_ERR_UNSUPPORTED.  A p_index entry outside [0, nP) -- or, with Htrue, an h_index entry outside [0, nH) -- fills that problem's
+ * H_hat with NaN and gives a NaN nmse (where given); nothing is read through the bad index and no other problem is affected.
+ * A refused call has written nothing; B = 0 is SBC_OK and launches nothing. */
 typedef struct sbc_ls_desc {
     const float* P;            /* [nP][Np][Nt] pilots (val_P, :109-111)                                                        */
     const int32_t* p_index;    /* [B] or NULL = b                                                                              */

@@ -77,8 +77,16 @@ __global__ __launch_bounds__(Geo<L>::THREADS) void l1_lifted_kernel(sbc_l1_lifte
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, g = lane >> 4;
     const int b = blockIdx.x, B = d.B, Np = d.Np;
     const int pi = d.p_index ? d.p_index[b] : b, hi = d.h_index ? d.h_index[b] : b;
-    if (pi < 0 || pi >= d.nP || hi < 0 || hi >= d.nH) {            // bad index: a NaN log, nothing read out of bounds
+    if (pi < 0 || pi >= d.nP || hi < 0 || hi >= d.nH) {            // bad index: NaN log and outputs, nothing read out of bounds
         for (int k = tid; k < d.steps; k += TH) d.nmse[(size_t)k * B + b] = NAN;
+        if (d.H_hat) {
+            float2* o = reinterpret_cast<float2*>(d.H_hat) + (size_t)b * NT * NR;
+            for (int e = tid; e < NT * NR; e += TH) o[e] = make_float2(NAN, NAN);
+        }
+        if (d.X) {
+            float2* o = reinterpret_cast<float2*>(d.X) + (size_t)b * N1 * N2;
+            for (int e = tid; e < N1 * N2; e += TH) o[e] = make_float2(NAN, NAN);
+        }
         return;
     }
     const float2* P = reinterpret_cast<const float2*>(d.P) + (size_t)pi * Np * NT;
@@ -231,18 +239,22 @@ __global__ __launch_bounds__(Geo<L>::THREADS) void l1_lifted_kernel(sbc_l1_lifte
         double err = 0.0;
         for (int job = wave; job < 8; job += NW) {
             const int tt = job >> 1, part = job & 1, ti_ = 16 * tt + c;
-            f4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
+            // the longest sum of a step (n1 terms per product): the two real products of the complex one are accumulated apart and added
+            // at the end, which halves the chain of dependent accumulations and its rounding error (H_hat element-wise against float64
+            // after 3 steps at L = 4: 1.1e-5 with one chain, 6e-6 with two; tests/test_gpu_cs_baselines.py::
+            // test_l1_first_steps_at_every_pilot_count).  Not unrolled: the second accumulator's registers come out of the unrolling.
+            f4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
+#pragma unroll 1
             for (int s = 0; s < N1 / 4; ++s) {
                 const int mm = 4 * s + g;
                 const float2 w = tw1[(ti_ * mm) & (N1 - 1)], tv = T[mm * US + c];
-                if (part == 0) { acc = mfma(w.x, tv.x, acc); acc = mfma(-w.y, tv.y, acc); }
-                else { acc = mfma(w.x, tv.y, acc); acc = mfma(w.y, tv.x, acc); }
+                if (part == 0) { a0 = mfma(w.x, tv.x, a0); a1 = mfma(-w.y, tv.y, a1); }
+                else { a0 = mfma(w.x, tv.y, a0); a1 = mfma(w.y, tv.x, a1); }
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int e = 2 * ((16 * tt + 4 * g + r) * NR + c) + part;
-                const float nv = acc[r], ov = Hxf[e];
+                const float nv = a0[r] + a1[r], ov = Hxf[e];
                 Hxf[e] = nv;
                 Hzf[e] = nv + cf * (nv - ov);
                 const float df = nv - Htf[e];
@@ -343,8 +355,11 @@ extern "C" int sbc_l1_lifted_run(const sbc_l1_lifted_desc* d, void* stream) {
         return SBC_ERR_UNSUPPORTED;
     }
     SBC_REQUIRE(d->B >= 0 && d->steps >= 1 && d->nP >= 1 && d->nH >= 1,
-                "sbc_l1_lifted_run: need B >= 0, steps >= 1, nP >= 1, nH >= 1 (got %d, %d, %d, %d)", d->B, d->steps, d->nP, d->nH);
-    SBC_REQUIRE(d->P && d->Y && d->Htrue && d->lmbda && d->lr && d->nmse, "sbc_l1_lifted_run: NULL input or nmse pointer");
+                "sbc_l1_lifted_run: need B >= 0, steps >= 1, nP >= 1, nH >= 1 (got B=%d steps=%d nP=%d nH=%d)", d->B, d->steps, d->nP,
+                d->nH);
+    const struct { const void* p; const char* name; } need[] = {{d->P, "P"}, {d->Y, "Y"}, {d->Htrue, "Htrue"}, {d->lmbda, "lmbda"},
+                                                                {d->lr, "lr"}, {d->nmse, "nmse"}};
+    for (const auto& q : need) SBC_REQUIRE(q.p, "sbc_l1_lifted_run: NULL %s", q.name);
     if (d->B == 0) return SBC_OK;
     hipStream_t s = (hipStream_t)stream;
     switch (d->lifting) {

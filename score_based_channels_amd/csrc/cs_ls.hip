@@ -4,18 +4,36 @@
 // equivalent form of size n = min(Np, Nt): with Np <= Nt,  H = P^H (P P^H + s2 I_Np)^-1 Y  (push-through identity); otherwise
 // the normal equations themselves.  One 256-thread workgroup per problem: the n x n matrix and the n x Nr right-hand side in
 // LDS, an in-place fp32 Cholesky factorisation M = L L^H, forward and back substitution, then H and its NMSE
-// ||H - Htrue||^2 / ||Htrue||^2 (test_ml.py:141-145).  Fixed summation orders throughout.
+// ||H - Htrue||^2 / ||Htrue||^2 (test_ml.py:141-145).  Fixed summation orders throughout.  The sums over Nt or Np (up to 1024 terms)
+// are added in blocks of 64 -- one term after the other inside a block, then block after block -- so that the rounding error of a
+// long sum grows like that of its blocks, not with its whole length; a sum of at most 64 terms is the plain running sum.
 #include "common.h"
 #include <math.h>
 
 namespace sbc {
 namespace {
 
-constexpr int LS_THREADS = 256, LS_MAX_N = 64, LS_MAX_NR = 64;
+constexpr int LS_THREADS = 256, LS_MAX_N = 64, LS_MAX_NR = 64, LS_BLOCK = 64;
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ float2 cmulc(float2 a, float2 b) {     // a * conj(b)
     return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y);
+}
+
+// sum_{t < len} term(t) in blocks of LS_BLOCK terms
+template <class F>
+__device__ __forceinline__ float2 blocked_sum(int len, F term) {
+    float2 acc = make_float2(0.f, 0.f);
+    for (int s = 0; s < len; s += LS_BLOCK) {
+        const int end = s + LS_BLOCK < len ? s + LS_BLOCK : len;
+        float2 part = make_float2(0.f, 0.f);
+        for (int t = s; t < end; ++t) {
+            const float2 v = term(t);
+            part.x += v.x; part.y += v.y;
+        }
+        acc.x += part.x; acc.y += part.y;
+    }
+    return acc;
 }
 
 __global__ __launch_bounds__(LS_THREADS) void ls_regularized_kernel(sbc_ls_desc d) {
@@ -31,6 +49,8 @@ __global__ __launch_bounds__(LS_THREADS) void ls_regularized_kernel(sbc_ls_desc 
     const int hi = d.Htrue ? (d.h_index ? d.h_index[b] : b) : 0;
     if (pi < 0 || pi >= d.nP || (d.Htrue && (hi < 0 || hi >= d.nH))) {  // bad index: NaN out, nothing read out of bounds
         if (d.nmse && tid == 0) d.nmse[b] = NAN;
+        float2* o = reinterpret_cast<float2*>(d.H_hat) + (size_t)b * Nt * Nr;
+        for (int e = tid; e < Nt * Nr; e += LS_THREADS) o[e] = make_float2(NAN, NAN);
         return;
     }
     const float2* P = reinterpret_cast<const float2*>(d.P) + (size_t)pi * Np * Nt;    // [Np][Nt]
@@ -40,18 +60,8 @@ __global__ __launch_bounds__(LS_THREADS) void ls_regularized_kernel(sbc_ls_desc 
     // M = P P^H + s2 I (small) or P^H P + s2 I;  R = Y or P^H Y
     for (int e = tid; e < n * n; e += LS_THREADS) {
         const int i = e / n, j = e % n;
-        float2 acc = make_float2(0.f, 0.f);
-        if (small) {
-            for (int t = 0; t < Nt; ++t) {
-                const float2 v = cmulc(P[i * Nt + t], P[j * Nt + t]);
-                acc.x += v.x; acc.y += v.y;
-            }
-        } else {
-            for (int p = 0; p < Np; ++p) {
-                const float2 v = cmulc(P[p * Nt + j], P[p * Nt + i]);        // conj(P[p][i]) P[p][j]
-                acc.x += v.x; acc.y += v.y;
-            }
-        }
+        float2 acc = small ? blocked_sum(Nt, [&](int t) { return cmulc(P[i * Nt + t], P[j * Nt + t]); })
+                           : blocked_sum(Np, [&](int p) { return cmulc(P[p * Nt + j], P[p * Nt + i]); });   // conj(P[p][i]) P[p][j]
         if (i == j) acc.x += s2;
         M[i * ms + j] = acc;
     }
@@ -60,12 +70,7 @@ __global__ __launch_bounds__(LS_THREADS) void ls_regularized_kernel(sbc_ls_desc 
         if (small) {
             R[e] = Y[e];
         } else {
-            float2 acc = make_float2(0.f, 0.f);
-            for (int p = 0; p < Np; ++p) {
-                const float2 v = cmulc(Y[p * Nr + q], P[p * Nt + i]);        // conj(P[p][i]) Y[p][q]
-                acc.x += v.x; acc.y += v.y;
-            }
-            R[e] = acc;
+            R[e] = blocked_sum(Np, [&](int p) { return cmulc(Y[p * Nr + q], P[p * Nt + i]); });   // conj(P[p][i]) Y[p][q]
         }
     }
     __syncthreads();
@@ -172,8 +177,10 @@ extern "C" int sbc_ls_regularized(const sbc_ls_desc* d, void* stream) {
                   d->Nt, d->Nr, d->Np, LS_MAX_N, LS_MAX_NR);
         return SBC_ERR_UNSUPPORTED;
     }
-    SBC_REQUIRE(d->B >= 0 && d->nP >= 1 && (!d->Htrue || d->nH >= 1), "sbc_ls_regularized: need B >= 0, nP >= 1 and nH >= 1");
-    SBC_REQUIRE(d->P && d->Y && d->noise_var && d->H_hat, "sbc_ls_regularized: NULL P, Y, noise_var or H_hat");
+    SBC_REQUIRE(d->B >= 0 && d->nP >= 1 && (!d->Htrue || d->nH >= 1),
+                "sbc_ls_regularized: need B >= 0, nP >= 1 and (with Htrue) nH >= 1 (got B=%d nP=%d nH=%d)", d->B, d->nP, d->nH);
+    const struct { const void* p; const char* name; } need[] = {{d->P, "P"}, {d->Y, "Y"}, {d->noise_var, "noise_var"}, {d->H_hat, "H_hat"}};
+    for (const auto& q : need) SBC_REQUIRE(q.p, "sbc_ls_regularized: NULL %s", q.name);
     SBC_REQUIRE(!d->nmse || d->Htrue, "sbc_ls_regularized: nmse needs Htrue");
     if (d->B == 0) return SBC_OK;
     const size_t lds = (4 + (size_t)n * (n + 1) + (size_t)n * d->Nr) * sizeof(float2);

@@ -5,6 +5,8 @@
   ``array_op = Compose((MatMul(Ld), RightMatMul(Rd)))`` = ``x -> Ld @ (x @ Rd)``, ``fw_op = Compose((MatMul(P), array_op))`` and
   ``fw_op.H`` = ``r -> (Ld^H @ (P^H @ r)) @ Rd^H``.  Batched over problems; float64 by default, complex64 on request.
 * ``lstsq_run``: the ``np.linalg.lstsq`` loop of ``test_ml.py:124-145``.
+* ``lstsq_run_c64``: the ML kernel's own formulation (include/sbc_hip.h: the system of size min(Np, Nt), Cholesky, two triangular
+  solves) restated in numpy complex64 -- the yardstick of what single precision can give at a problem's conditioning.
 * ``l1_script`` / ``ml_script``: the two scripts' main loops (test_l1Fourier_lifted.py:45-211, test_ml.py:45-154) on the package's
   loader (synthetic channels) with numpy's legacy global RNG seeded once, the solvers replaced by the restatements above -- the
   precedent of ``gen_golden.reference_ald``.
@@ -14,6 +16,7 @@ import itertools
 
 import numpy as np
 from scipy.fft import ifft
+from scipy.linalg import solve_triangular
 
 from score_based_channels_amd.config import Config, default_config
 from score_based_channels_amd.loaders import Channels
@@ -63,9 +66,10 @@ def t_sequence(steps):
     return np.asarray(ts), np.asarray(cs)
 
 
-def l1_run(P, Y, H, lmbda, lr, lifting=4, steps=1000, dtype=np.complex128):
+def l1_run(P, Y, H, lmbda, lr, lifting=4, steps=1000, dtype=np.complex128, return_v=False):
     """Batched restatement of :145-189.  ``P`` [B, Np, Nt], ``Y`` [B, Np, Nr], ``H`` [B, Nt, Nr]; ``lmbda`` / ``lr`` scalars or [B].
-    Returns (log [steps, B] float64, H_hat [B, Nt, Nr], X [B, L Nt, L Nr])."""
+    Returns (log [steps, B] float64, H_hat [B, Nt, Nr], X [B, L Nt, L Nr]); with ``return_v`` also the last step's argument of the
+    soft threshold, ``v = z - lr grad f(z)`` [B, L Nt, L Nr] (``X = soft_thresh(lmbda lr, v)``)."""
     rdt = np.float32 if dtype == np.complex64 else np.float64
     P, Y, H = (np.asarray(a).astype(dtype) for a in (P, Y, H))
     B, _, nt = P.shape
@@ -79,17 +83,18 @@ def l1_run(P, Y, H, lmbda, lr, lifting=4, steps=1000, dtype=np.complex128):
     t = 1.0
     hn = np.sum(np.abs(H.astype(np.complex128)) ** 2, axis=(-1, -2))
     log = np.empty((steps, B))
-    est = None
+    est = v = None
     for k in range(steps):
         x_old = x
         g = fw_op_H(P, Ld, Rd, fw_op(P, Ld, Rd, z) - Y)          # gradf(x) = fw_op.H * (fw_op * x - y), at x = z
-        x = soft_thresh(tau, z - lrs * g)                          # axpy(x, -alpha, gradf(x)); proxg(alpha, x)
+        v = z - lrs * g                                            # axpy(x, -alpha, gradf(x))
+        x = soft_thresh(tau, v)                                    # proxg(alpha, x)
         t_old = t
         t = (1 + (1 + 4 * t_old ** 2) ** 0.5) / 2
         z = x + dtype((t_old - 1) / t) * (x - x_old)
         est = array_op(Ld, Rd, x)
         log[k] = np.sum(np.abs((est - H).astype(np.complex128)) ** 2, axis=(-1, -2)) / hn
-    return log, est, x
+    return (log, est, x, v) if return_v else (log, est, x)
 
 
 def lstsq_run(P, Y, H, noise):
@@ -103,6 +108,41 @@ def lstsq_run(P, Y, H, noise):
         normal_Y = np.matmul(P[b].T.conj(), Y[b])
         est[b] = np.linalg.lstsq(normal_P, normal_Y, rcond=None)[0]
         nmse[b] = np.sum(np.abs(est[b] - H[b]) ** 2) / np.sum(np.abs(H[b]) ** 2)
+    return est, nmse
+
+
+def lstsq_run_c64(P, Y, H, noise):
+    """The formulation of ``sbc_ls_regularized`` (include/sbc_hip.h, csrc/cs_ls.hip) in complex64 / float32, per problem, with
+    ``s2 = float32(noise)`` and ``n = min(Np, Nt)``:
+
+    * ``Np <= Nt`` (push-through): ``M = P P^H + s2 I_Np``, ``R = Y``, and after the solve ``H_hat = P^H W``;
+    * ``Np > Nt`` (normal equations): ``M = P^H P + s2 I_Nt``, ``R = P^H Y``, ``H_hat = W``;
+
+    ``M = L L^H`` by LAPACK's single-precision Cholesky, ``L Z = R``, ``L^H W = Z``.  Every array stays complex64; only the NMSE
+    (fp32 differences, float64 sum, as the kernel forms it) is float64.  Returns (H_hat [B, Nt, Nr] complex64, nmse [B] float64;
+    NaN where ``H`` is None).  A matrix that is not positive definite in single precision gives NaN for that problem."""
+    P, Y = np.asarray(P).astype(np.complex64), np.asarray(Y).astype(np.complex64)
+    B, npil, nt = P.shape
+    s2 = np.broadcast_to(np.asarray(noise, np.float64), (B,)).astype(np.float32)
+    est = np.empty((B, nt, Y.shape[2]), np.complex64)
+    nmse = np.full(B, np.nan)
+    small = npil <= nt
+    for b in range(B):
+        Ph = np.conj(P[b].T)
+        M, R = (P[b] @ Ph, Y[b]) if small else (Ph @ P[b], Ph @ Y[b])
+        M = M + (s2[b] * np.eye(M.shape[0], dtype=np.float32)).astype(np.complex64)
+        try:
+            Lc = np.linalg.cholesky(M)
+        except np.linalg.LinAlgError:
+            est[b] = np.nan
+            continue
+        Z = solve_triangular(Lc, R, lower=True, check_finite=False)
+        W = solve_triangular(np.conj(Lc.T), Z, lower=False, check_finite=False)
+        est[b] = Ph @ W if small else W
+        assert M.dtype == Lc.dtype == Z.dtype == W.dtype == np.complex64
+        if H is not None:
+            Hb = np.asarray(H[b]).astype(np.complex64)
+            nmse[b] = np.sum(np.abs((est[b] - Hb).astype(np.complex128)) ** 2) / np.sum(np.abs(Hb.astype(np.complex128)) ** 2)
     return est, nmse
 
 

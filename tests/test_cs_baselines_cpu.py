@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import cs_checks as K
 import cs_oracle as O
 from score_based_channels_amd import baselines, test_l1Fourier_lifted as l1cli, test_ml as mlcli
 
@@ -122,3 +123,119 @@ def test_ls_regularized_refuses_bad_arguments_on_the_host():
     with pytest.raises(ValueError, match='supports'):
         big = np.zeros((1, 100, 100), np.complex64)
         baselines.ls_regularized(big, np.zeros((1, 100, 16), np.complex64), 0.1)
+
+
+# ---- the single-precision restatement of the ML solver and the assertion helpers of the GPU tests (tests/cs_checks.py)
+
+@pytest.mark.parametrize('npil,nt,nr', K.LS_GRID)
+def test_ls_c64_restatement_on_the_geometry_grid(npil, nt, nr):
+    """lstsq_run_c64 factorises every problem of the grid (no NaN at kappa up to ~1e5), stays within the forward-error bound of a
+    single-precision Cholesky solve -- gamma_{3n+1} kappa for the solve (Higham, Accuracy and Stability, thm 10.4) plus
+    (Np + Nt) u for the products around it -- of lstsq_run, and passes the GPU test's own check when offered as the answer."""
+    P, Y, H, pidx, hidx, noise = K.ls_problem(npil, nt, nr, 1000 + 7 * npil + nt + nr)
+    Pb, Hb = P[pidx], H[hidx]
+    cH, cn = O.lstsq_run_c64(Pb, Y, Hb, noise)
+    assert cH.dtype == np.complex64 and np.all(np.isfinite(K.ri(cH))) and np.all(np.isfinite(cn))
+    figures, failures = K.check_ls(cH, cn.astype(np.float32), Pb, Y, Hb, noise)
+    print(figures)
+    assert not failures, failures
+    assert len(figures) == 4 and all(f['c_over_theory'] <= 1 for f in figures)
+
+
+def test_ls_grid_holds_what_the_library_documents():
+    assert len(K.LS_GRID) == 18 and len(set(K.LS_GRID)) == 18
+    assert sum(npil > nt for npil, nt, _ in K.LS_GRID) >= 5
+    assert all(min(npil, nt) <= baselines.LS_MAX_N and nr <= baselines.LS_MAX_NR and max(npil, nt) <= baselines.LS_MAX_DIM
+               for npil, nt, nr in K.LS_GRID)
+    assert {(63, 64, 17), (64, 64, 64), (65, 64, 16), (1024, 64, 16), (64, 1024, 16), (1, 1, 1), (2, 3, 1)} <= set(K.LS_GRID)
+    n, nr = 64, 64
+    assert (4 + n * (n + 1) + n * nr) * 8 > 64 * 1024           # the (64, 64, 64) case asks for more than 64 KiB of LDS
+
+
+@pytest.mark.parametrize('npil,nt,nr', [(76, 64, 16), (100, 33, 5), (7, 5, 3)])
+def test_check_ls_trips_on_a_wrong_normal_equations_branch(npil, nt, nr):
+    """Mutation of the yardstick: the Np > Nt right-hand side un-conjugated (P^T Y for P^H Y), and the system solved with the
+    regulariser's sign flipped -- each trips check_ls, the second one on the residual and the NMSE as well."""
+    P, Y, H, pidx, hidx, noise = K.ls_problem(npil, nt, nr, 5)
+    Pb, Hb = P[pidx], H[hidx]
+    good, gn = O.lstsq_run_c64(Pb, Y, Hb, noise)
+    assert not K.check_ls(good, gn.astype(np.float32), Pb, Y, Hb, noise)[1]
+    eye = np.eye(nt, dtype=np.complex64)
+    unconj = np.stack([np.linalg.solve(np.conj(Pb[b].T) @ Pb[b] + np.float32(noise[b]) * eye, Pb[b].T @ Y[b]) for b in range(16)])
+    _, failures = K.check_ls(unconj.astype(np.complex64), None, Pb, Y, Hb, noise)
+    assert any('H_hat error' in f for f in failures) and any('residual' in f for f in failures), failures
+    minus = np.stack([np.linalg.solve(np.conj(Pb[b].T) @ Pb[b] - np.float32(noise[b]) * eye, np.conj(Pb[b].T) @ Y[b])
+                      for b in range(16)]).astype(np.complex64)
+    mn = np.sum(np.abs(minus - Hb) ** 2, axis=(1, 2)) / np.sum(np.abs(Hb) ** 2, axis=(1, 2))
+    _, failures = K.check_ls(minus, mn.astype(np.float32), Pb, Y, Hb, noise)
+    assert any('residual' in f for f in failures) and any('nmse' in f for f in failures), failures
+    # a right answer with a wrong NMSE (that of another problem), and a NaN, trip too
+    _, failures = K.check_ls(good, np.roll(gn, 1).astype(np.float32), Pb, Y, Hb, noise)
+    assert any('nmse' in f for f in failures), failures
+    bad = good.copy()
+    bad[3, 0, 0] = np.nan
+    assert 'non-finite H_hat or nmse' in K.check_ls(bad, None, Pb, Y, Hb, noise)[1]
+
+
+def _l1_data(B, npil, seed):
+    rng = np.random.default_rng(seed)
+    P, Y, H = (a.astype(np.complex64) for a in _problem(rng, B=B, np_=npil))
+    return P, Y, H
+
+
+@pytest.mark.parametrize('L', [1, 2, 4])
+def test_half_sparse_lambda_on_the_gpu_tests_data(L):
+    """On the very problems of the GPU test (cdl_data(4, 38, 31, 10 dB)): the threshold bites -- half of the first iterate is zero
+    and more later --, the complex64 oracle has the float64 oracle's support outside the excused window (1e-5 max|v| around the
+    threshold) and meets the value bounds, and the window holds at most 0.1 % of X per problem."""
+    P, Y, H = K.cdl_data(4, 38, 31, 10.0)
+    lam = K.half_sparse_lambda(P, Y, L)
+    for steps in (1, 2, 3, 10):
+        rlog, rH, rX, rv = O.l1_run(P, Y, H, lam, 3e-3, L, steps, return_v=True)
+        clog, cH, cX = O.l1_run(P, Y, H, lam, 3e-3, L, steps, dtype=np.complex64)
+        figures, failures = K.check_l1_iterate(clog, cH, cX, rlog, rH, rX, rv, lam * 3e-3)
+        print(L, steps, figures)
+        assert not failures, failures
+        assert 0.45 <= figures['zero_share'][0] and figures['zero_share'][1] <= 0.85
+        if steps == 1:
+            assert figures['zero_share'] == (0.5, 0.5)
+        assert np.array_equal(rX, O.soft_thresh((lam * 3e-3)[:, None, None], rv))
+
+
+def test_check_l1_iterate_trips_on_a_threshold_of_lambda_instead_of_lambda_lr():
+    """Mutation of the yardstick: tau = lambda (an oracle run at lambda / lr) offered as the answer."""
+    P, Y, H = _l1_data(2, 38, 4)
+    lam, lr = K.half_sparse_lambda(P, Y, 2), 3e-3
+    rlog, rH, rX, rv = O.l1_run(P, Y, H, lam, lr, 2, 2, return_v=True)
+    wlog, wH, wX = O.l1_run(P, Y, H, lam / lr, lr, 2, 2, dtype=np.complex64)
+    _, failures = K.check_l1_iterate(wlog, wH, wX, rlog, rH, rX, rv, lam * lr)
+    assert any('differ in support' in f for f in failures) and any(f.startswith('log') for f in failures), failures
+    # one entry away from the threshold switched off: the support check alone trips
+    clog, cH, cX = O.l1_run(P, Y, H, lam, lr, 2, 2, dtype=np.complex64)
+    i = np.unravel_index(np.argsort(np.abs(rX[0]).ravel())[-rX[0].size // 4], rX[0].shape)
+    cX[0][i] = 0
+    _, failures = K.check_l1_iterate(clog, cH, cX, rlog, rH, rX, rv, lam * lr)
+    assert any('differ in support' in f for f in failures), failures
+
+
+def test_check_l1_consistency_trips_on_a_wrong_dictionary(monkeypatch):
+    """Mutation of the yardstick: at L = 2 the forward product formed with the right dictionary of L = 4 truncated to its first
+    32 rows; and a log that belongs to the previous iterate."""
+    P, Y, H = _l1_data(2, 38, 6)
+    log, Hh, X = O.l1_run(P, Y, H, 0.3, 3e-3, 2, 5, dtype=np.complex64)
+    figures, failures = K.check_l1_consistency(log[-1].astype(np.float32), Hh, X, H, 2)
+    assert not failures, (figures, failures)
+    Ld, _ = O.dictionaries(64, 16, 2)
+    _, Rd4 = O.dictionaries(64, 16, 4)
+    wrong = O.array_op(Ld, Rd4[:32], X.astype(np.complex128)).astype(np.complex64)
+    wl = np.sum(np.abs(wrong - H) ** 2, axis=(1, 2)) / np.sum(np.abs(H) ** 2, axis=(1, 2))
+    _, failures = K.check_l1_consistency(wl.astype(np.float32), wrong, X, H, 2)
+    assert failures == [f for f in failures if 'not Ld X Rd' in f] and failures
+    _, failures = K.check_l1_consistency(log[-2].astype(np.float32), Hh, X, H, 2)
+    assert failures and all('log[-1]' in f for f in failures), failures
+    # the same mutation through the oracle: a run with the truncated dictionary is caught by the step comparison
+    monkeypatch.setattr(O, 'dictionaries', lambda nt, nr, L: (Ld, Rd4[:32]))
+    wlog, wH, wX = O.l1_run(P, Y, H, 0.3, 3e-3, 2, 3, dtype=np.complex64)
+    monkeypatch.undo()
+    rlog, rH, rX = O.l1_run(P, Y, H, 0.3, 3e-3, 2, 3)
+    assert K.check_l1_iterate(wlog, wH, wX, rlog, rH, rX)[1]

@@ -189,3 +189,207 @@ def test_plan_refuses_inconsistent_lanes():
         with pytest.raises(_lib.SbcError, match=what):
             _lib.Plan(bad)
     del x
+
+
+# ---- the classical baselines (sbc_l1_lifted_run, sbc_ls_regularized) through the raw ABI: descriptors filled by hand from torch
+# device pointers, so that the library's own checks are reached (baselines.py refuses bad input on the host first)
+
+OK, INVALID, UNSUPPORTED = 0, -1, -3
+SENTINEL = 7.0
+
+
+class _Case:
+    """Device tensors of B problems (QPSK pilots, Gaussian channels: cs_checks.ls_problem) and the two descriptors over them.
+    ``spare``: that many extra matrices in front of and behind the nP / nH the descriptor declares (the descriptor's P / Htrue
+    point at the first declared one), so that the indices -1 and nP / nH stay inside the allocation."""
+
+    def __init__(self, B, npil, nt=64, nr=16, L=2, steps=5, nP=None, nH=None, spare=0, seed=3):
+        import torch
+        import cs_checks as K
+        nP, nH = nP or B, nH or B
+        P, _, H, _, _, noise = K.ls_problem(npil, nt, nr, seed, B=B, nP=nP + 2 * spare, nH=nH + 2 * spare, noises=(0.1, 1.0))
+        self.B, self.nP, self.nH, self.nt, self.nr, self.npil, self.L, self.steps, self.spare = B, nP, nH, nt, nr, npil, L, steps, spare
+        self.pidx_np, self.hidx_np = np.arange(B) % nP, (np.arange(B) + 1) % nH
+        rng = np.random.default_rng(seed)
+        z = rng.standard_normal((B, npil, nr)) + 1j * rng.standard_normal((B, npil, nr))
+        Y = (P[spare + self.pidx_np] @ H[spare + self.hidx_np] + 0.2 * z).astype(np.complex64)   # of the DECLARED matrices
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        self.P, self.Y, self.H = dev(P), dev(Y), dev(H)
+        self.pidx, self.hidx = dev(self.pidx_np.astype(np.int32)), dev(self.hidx_np.astype(np.int32))
+        self.lam, self.lr, self.nv = dev(np.full(B, 0.3, np.float32)), dev(np.full(B, 3e-3, np.float32)), dev(noise.astype(np.float32))
+        self.fresh()
+
+    def fresh(self):
+        import torch
+        full = lambda *shape: torch.full(shape, SENTINEL, dtype=torch.float32, device='cuda')
+        self.log, self.nmse = full(self.steps, self.B), full(self.B)
+        self.Hh, self.X = full(self.B, self.nt, self.nr, 2), full(self.B, self.L * self.nt, self.L * self.nr, 2)
+        return self
+
+    def untouched(self):
+        import torch
+        torch.cuda.synchronize()
+        return all(bool((t == SENTINEL).all()) for t in (self.log, self.nmse, self.Hh, self.X))
+
+    def _base(self, t):
+        return t.data_ptr() + self.spare * t[0].numel() * 8
+
+    def l1(self, **over):
+        from score_based_channels_amd import _lib
+        f = dict(P=self._base(self.P), p_index=self.pidx.data_ptr(), Y=self.Y.data_ptr(), Htrue=self._base(self.H),
+                 h_index=self.hidx.data_ptr(), lmbda=self.lam.data_ptr(), lr=self.lr.data_ptr(), nmse=self.log.data_ptr(),
+                 H_hat=self.Hh.data_ptr(), X=self.X.data_ptr(), B=self.B, nP=self.nP, nH=self.nH, Nt=self.nt, Nr=self.nr, Np=self.npil,
+                 lifting=self.L, steps=self.steps)
+        f.update(over)
+        return _lib.sbc_l1_lifted_desc(**f)
+
+    def ls(self, **over):
+        from score_based_channels_amd import _lib
+        f = dict(P=self._base(self.P), p_index=self.pidx.data_ptr(), Y=self.Y.data_ptr(), noise_var=self.nv.data_ptr(),
+                 Htrue=self._base(self.H), h_index=self.hidx.data_ptr(), H_hat=self.Hh.data_ptr(), nmse=self.nmse.data_ptr(), B=self.B,
+                 nP=self.nP, nH=self.nH, Nt=self.nt, Nr=self.nr, Np=self.npil)
+        f.update(over)
+        return _lib.sbc_ls_desc(**f)
+
+
+def _call(fn, desc, stream=None):
+    """(status, sbc_last_error text) of one call on ``stream`` (default: torch's current stream), synchronised"""
+    import torch
+    from score_based_channels_amd import _lib
+    s = stream if stream is not None else torch.cuda.current_stream()
+    rc = getattr(_lib.lib(), fn)(C.byref(desc) if desc is not None else None, C.c_void_p(s.cuda_stream))
+    s.synchronize()
+    return rc, _lib.lib().sbc_last_error().decode()
+
+
+def _bits(*tensors):
+    return b''.join(t.cpu().numpy().tobytes() for t in tensors)
+
+
+L1_REFUSALS = [(dict(Nt=32), UNSUPPORTED, 'Nt=32'), (dict(Nr=8), UNSUPPORTED, 'Nr=8'), (dict(lifting=3), UNSUPPORTED, 'lifting=3'),
+               (dict(Np=0), UNSUPPORTED, 'Np=0'), (dict(Np=65), UNSUPPORTED, 'Np=65'), (dict(steps=0), INVALID, 'steps=0'),
+               (dict(nP=0), INVALID, 'nP=0'), (dict(nH=0), INVALID, 'nH=0'), (dict(B=-1), INVALID, 'B=-1')] + \
+              [({k: None}, INVALID, 'NULL %s' % k) for k in ('P', 'Y', 'Htrue', 'lmbda', 'lr', 'nmse')]
+LS_REFUSALS = [(dict(Nr=65), UNSUPPORTED, 'Nr=65'), (dict(Np=65, Nt=65), UNSUPPORTED, 'Np=65'), (dict(Nt=1025), UNSUPPORTED, 'Nt=1025'),
+               (dict(Np=1025), UNSUPPORTED, 'Np=1025'), (dict(Nt=0), UNSUPPORTED, 'Nt=0'), (dict(Htrue=None), INVALID, 'nmse needs Htrue'),
+               (dict(nP=0), INVALID, 'nP=0'), (dict(nH=0), INVALID, 'nH=0'), (dict(B=-1), INVALID, 'B=-1')] + \
+              [({k: None}, INVALID, 'NULL %s' % k) for k in ('P', 'Y', 'noise_var', 'H_hat')]
+
+
+@pytest.mark.parametrize('fn,table', [('sbc_l1_lifted_run', L1_REFUSALS), ('sbc_ls_regularized', LS_REFUSALS)])
+def test_baseline_calls_refuse_what_the_header_excludes(fn, table):
+    """Each refusal of the library itself: its status code, a message that names the function and the offending value, and no
+    output buffer written (they hold a sentinel)."""
+    c = _Case(4, 38)
+    make = c.l1 if fn == 'sbc_l1_lifted_run' else c.ls
+    for over, status, text in table:
+        rc, msg = _call(fn, make(**over))
+        assert rc == status and fn in msg and text in msg, (over, rc, msg)
+        assert c.untouched(), over
+    rc, msg = _call(fn, None)
+    assert rc == INVALID and fn in msg and 'NULL descriptor' in msg
+    # B = 0: fine, and nothing launched
+    rc, _ = _call(fn, make(B=0))
+    assert rc == OK and c.untouched()
+    # and the same descriptor unmodified runs
+    rc, msg = _call(fn, make())
+    assert rc == OK, msg
+    assert not c.untouched()
+
+
+@pytest.mark.parametrize('L', [1, 2, 4])
+def test_l1_call_optional_outputs_and_index_maps(L):
+    """H_hat = NULL, X = NULL, both: the log has the same bits and the output that is given too; p_index / h_index = NULL with
+    nP = nH = B is the identity map."""
+    c = _Case(5, 25, L=L, steps=6)
+    ident = np.arange(5, dtype=np.int32)
+    import torch
+    c.pidx, c.hidx = torch.from_numpy(ident).cuda(), torch.from_numpy(ident).cuda()
+    assert _call('sbc_l1_lifted_run', c.l1())[0] == OK
+    log, Hh, X = _bits(c.log), _bits(c.Hh), _bits(c.X)
+    assert np.all(np.isfinite(c.log.cpu().numpy()))
+    for over in (dict(H_hat=None), dict(X=None), dict(H_hat=None, X=None), dict(p_index=None), dict(h_index=None),
+                 dict(p_index=None, h_index=None)):
+        c.fresh()
+        rc, msg = _call('sbc_l1_lifted_run', c.l1(**over))
+        assert rc == OK, msg
+        assert _bits(c.log) == log, over
+        assert bool((c.Hh == SENTINEL).all()) if 'H_hat' in over else _bits(c.Hh) == Hh, over
+        assert bool((c.X == SENTINEL).all()) if 'X' in over else _bits(c.X) == X, over
+
+
+@pytest.mark.parametrize('npil,nt,nr', [(25, 64, 16), (70, 33, 5)])
+def test_ls_call_optional_outputs_and_index_maps(npil, nt, nr):
+    """Htrue = nmse = NULL: the same H_hat bits, nmse untouched; NULL index maps with nP = nH = B are the identity."""
+    import torch
+    c = _Case(6, npil, nt, nr)
+    ident = np.arange(6, dtype=np.int32)
+    c.pidx, c.hidx = torch.from_numpy(ident).cuda(), torch.from_numpy(ident).cuda()
+    assert _call('sbc_ls_regularized', c.ls())[0] == OK
+    Hh, nmse = _bits(c.Hh), _bits(c.nmse)
+    assert np.all(np.isfinite(c.nmse.cpu().numpy())) and np.all(np.isfinite(c.Hh.cpu().numpy()))
+    for over in (dict(Htrue=None, h_index=None, nmse=None, nH=0), dict(nmse=None), dict(p_index=None), dict(h_index=None),
+                 dict(p_index=None, h_index=None)):
+        c.fresh()
+        rc, msg = _call('sbc_ls_regularized', c.ls(**over))
+        assert rc == OK, msg
+        assert _bits(c.Hh) == Hh, over
+        assert bool((c.nmse == SENTINEL).all()) if 'nmse' in over else _bits(c.nmse) == nmse, over
+
+
+def test_baseline_calls_on_a_callers_stream():
+    """A non-default stream: the same bits as on the default stream once that stream is synchronised."""
+    import torch
+    c = _Case(6, 51, L=4, steps=8)
+    assert _call('sbc_l1_lifted_run', c.l1())[0] == OK
+    want_l1 = _bits(c.log, c.Hh, c.X)
+    c.fresh()
+    assert _call('sbc_ls_regularized', c.ls())[0] == OK
+    want_ls = _bits(c.Hh, c.nmse)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    c.fresh()
+    torch.cuda.synchronize()
+    assert _call('sbc_l1_lifted_run', c.l1(), side)[0] == OK
+    assert _bits(c.log, c.Hh, c.X) == want_l1
+    c.fresh()
+    torch.cuda.synchronize()
+    assert _call('sbc_ls_regularized', c.ls(), side)[0] == OK
+    assert _bits(c.Hh, c.nmse) == want_ls
+
+
+def test_baseline_calls_mark_out_of_range_indices_with_nan():
+    """include/sbc_hip.h: an index outside [0, nP) / [0, nH) gives that problem a NaN log (l1) / nmse (ML) and NaN H_hat / X,
+    reads nothing through the bad index and leaves every other problem as it is.  Both kernels test ``idx < 0 || idx >= n``
+    before forming any address from it (cs_l1.hip, cs_ls.hip: first statement after the index loads).  The case is safe even
+    against a wrong guard: P and H hold one spare matrix in front of and behind the declared ones, and only -1 and nP / nH are
+    used.  One launch per solver."""
+    import torch
+    c = _Case(8, 38, L=2, steps=5, nP=4, nH=4, spare=1)
+    assert _call('sbc_l1_lifted_run', c.l1())[0] == OK
+    log, Hh, X = c.log.cpu().numpy(), c.Hh.cpu().numpy(), c.X.cpu().numpy()
+    c.fresh()
+    assert _call('sbc_ls_regularized', c.ls())[0] == OK
+    lsH, lsn = c.Hh.cpu().numpy(), c.nmse.cpu().numpy()
+    assert np.all(np.isfinite(log)) and np.all(np.isfinite(lsn))
+    pb, hb = c.pidx_np.astype(np.int32), c.hidx_np.astype(np.int32)
+    pb[1], pb[3], hb[4], hb[6] = -1, c.nP, -1, c.nH
+    bad, good = [1, 3, 4, 6], [0, 2, 5, 7]
+    c.pidx, c.hidx = torch.from_numpy(pb).cuda(), torch.from_numpy(hb).cuda()
+    c.fresh()
+    assert _call('sbc_l1_lifted_run', c.l1())[0] == OK
+    log1, Hh1, X1 = c.log.cpu().numpy(), c.Hh.cpu().numpy(), c.X.cpu().numpy()
+    assert np.all(np.isnan(log1[:, bad])) and np.all(np.isnan(Hh1[bad])) and np.all(np.isnan(X1[bad]))
+    assert log1[:, good].tobytes() == log[:, good].tobytes() and Hh1[good].tobytes() == Hh[good].tobytes()
+    assert X1[good].tobytes() == X[good].tobytes()
+    c.fresh()
+    assert _call('sbc_ls_regularized', c.ls())[0] == OK
+    lsH1, lsn1 = c.Hh.cpu().numpy(), c.nmse.cpu().numpy()
+    assert np.all(np.isnan(lsn1[bad])) and np.all(np.isnan(lsH1[bad]))
+    assert lsn1[good].tobytes() == lsn[good].tobytes() and lsH1[good].tobytes() == lsH[good].tobytes()
+    # without Htrue the channel map is not looked at: only the bad pilot indices are marked
+    c.fresh()
+    assert _call('sbc_ls_regularized', c.ls(Htrue=None, nmse=None))[0] == OK
+    lsH2 = c.Hh.cpu().numpy()
+    assert np.all(np.isnan(lsH2[[1, 3]])) and np.delete(lsH2, [1, 3], axis=0).tobytes() == np.delete(lsH, [1, 3], axis=0).tobytes()
+    assert bool((c.nmse == SENTINEL).all())

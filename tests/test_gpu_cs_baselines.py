@@ -4,28 +4,15 @@ import numpy as np
 import pytest
 import torch
 
+import cs_checks as K
 import cs_oracle as O
-from conftest import rel_err_elementwise
+from conftest import rel_err, rel_err_elementwise
 
 pytestmark = pytest.mark.gpu
 
 
-def _data(B, npil, seed, snr_db, channels=None):
-    """B synthetic CDL-C channels [B, 64, 16], QPSK pilots [B, Np, 64], measurements at snr_db ([B] or scalar) -- complex64."""
-    from score_based_channels_amd import synth
-    raw = synth.generate_channels('CDL-C', B, 64, 16, 0.5, seed) if channels is None else channels
-    H = np.conj(np.transpose(raw / np.std(raw), (0, 2, 1))).astype(np.complex64)
-    rng = np.random.default_rng(seed)
-    P = np.conj(np.transpose(synth.qpsk_pilots(rng, B, 64, npil), (0, 2, 1))).astype(np.complex64)
-    noise = 10 ** (-np.broadcast_to(np.asarray(snr_db, np.float64), (B,)) / 10.) * 16
-    z = (rng.standard_normal((B, npil, 16)) + 1j * rng.standard_normal((B, npil, 16))) / np.sqrt(2)
-    Y = (P @ H + np.sqrt(noise)[:, None, None] * z).astype(np.complex64)
-    return P, Y, H
-
-
-def _ri(a):
-    """complex -> interleaved (re, im) components, for the element-wise comparison of conftest.rel_err_elementwise"""
-    return np.ascontiguousarray(a).astype(np.complex128).view(np.float64)
+_data = K.cdl_data
+_ri = K.ri
 
 
 def _gpu_l1(P, Y, H, lam, lr, L, steps, **kw):
@@ -51,17 +38,102 @@ def test_l1_first_steps_match_the_oracle(L, steps):
     assert np.max(np.abs(log / rlog - 1)) < 5e-6
 
 
-@pytest.mark.parametrize('L', [1, 4])
-def test_l1_full_run_log_matches_the_oracle(L):
-    snrs, lams, per = [-10.0, 10.0, 30.0], [0.0, 0.3], 2
-    cells = [(s, lam) for s in snrs for lam in lams]
-    B = len(cells) * per
-    snr = np.repeat([c[0] for c in cells], per)
-    lam = np.repeat([c[1] for c in cells], per)
-    P, Y, H = _data(B, 38, 21, snr)
+@pytest.mark.parametrize('L', [1, 2, 4])
+@pytest.mark.parametrize('npil', [1, 2, 12, 25, 51, 63, 64])
+def test_l1_first_steps_at_every_pilot_count(npil, L):
+    """Np decides G = P^H P, b = P^H Y and the loop bounds of the prologue: the reference's alpha grid (12, 25, 38, 51, 64), the
+    ends of the documented range and an odd neighbour, 3 steps, the bounds of test_l1_first_steps_match_the_oracle."""
+    P, Y, H = _data(3, npil, 100 + npil, 10.0)
+    log, Hh, X = _gpu_l1(P, Y, H, 0.3, 3e-3, L, 3, want_x=True)
+    rlog, rH, rX = O.l1_run(P, Y, H, 0.3, 3e-3, L, 3)
+    clog, cH, cX = O.l1_run(P, Y, H, 0.3, 3e-3, L, 3, dtype=np.complex64)
+    fc, failures = K.check_l1_iterate(clog, cH, cX, rlog, rH, rX)
+    assert not failures, failures                               # the oracle itself in complex64 meets the bounds
+    fk, failures = K.check_l1_iterate(log, Hh, X, rlog, rH, rX)
+    print('l1 3 steps Np=%d L=%d: kernel %s, complex64 oracle %s, H_hat norm-wise %.3g' % (npil, L, fk, fc, rel_err(Hh, rH)))
+    assert not failures, failures
+
+
+@pytest.mark.parametrize('L', [1, 2, 4])
+@pytest.mark.parametrize('steps', [1, 2, 3, 10])
+def test_l1_partly_sparse_iterate_matches_the_oracle(L, steps):
+    """The regime fsAD exists for: lambda per problem at the median of the first gradient step, so that half of the first iterate
+    is zero and more later (float64 oracle on these problems: 50 / 52 / 53 / 70 % zeros after 1 / 2 / 3 / 10 steps at L = 1,
+    50 / 53 / 56 / 76 % at L = 4).  The zero pattern of X equals the oracle's exactly except where the oracle's pre-threshold |v|
+    lies within 1e-5 max|v| of the threshold -- at most 0.073 % of X per problem on these data (3 of 4096 entries at L = 2) (tests/test_cs_baselines_cpu.py::
+    test_half_sparse_lambda_on_the_gpu_tests_data; cap 0.1 %) -- and the values meet the bounds of the first-steps test."""
+    P, Y, H = _data(4, 38, 31, 10.0)
+    lam = K.half_sparse_lambda(P, Y, L)
+    log, Hh, X = _gpu_l1(P, Y, H, lam, 3e-3, L, steps, want_x=True)
+    rlog, rH, rX, rv = O.l1_run(P, Y, H, lam, 3e-3, L, steps, return_v=True)
+    figures, failures = K.check_l1_iterate(log, Hh, X, rlog, rH, rX, rv, lam * 3e-3)
+    print('l1 partly sparse L=%d steps=%d: %s' % (L, steps, figures))
+    assert not failures, failures
+    assert 0.45 <= figures['zero_share'][0] and figures['zero_share'][1] <= 0.85 and np.mean(X == 0) >= 0.45
+
+
+@pytest.mark.parametrize('L', [1, 2, 4])
+def test_l1_thousand_steps_are_self_consistent(L):
+    """Free of the null-space drift that limits the comparison with the oracle after 1000 steps: the returned H_hat, X and
+    log[-1] are one iterate (cs_checks.check_l1_consistency: H_hat = Ld X Rd to 1e-5 element-wise, log[-1] = NMSE of H_hat to
+    1e-6), with and without the l1 term; and the step loop does not depend on ``steps``: a run of k steps gives the first k log
+    rows of the 1000-step run bit for bit, and its own H_hat / X / log[-1] are consistent in the same way."""
+    lam = np.array([0.0, 0.3, 0.0, 0.3])
+    P, Y, H = _data(4, 38, 61, np.array([10.0, 10.0, 30.0, -10.0]))
+    log, Hh, X = _gpu_l1(P, Y, H, lam, 3e-3, L, 1000, want_x=True)
+    assert np.all(np.isfinite(log))
+    figures, failures = K.check_l1_consistency(log[-1], Hh, X, H, L)
+    print('l1 self-consistency L=%d after 1000 steps: %s' % (L, figures))
+    assert not failures, failures
+    for k in (1, 7, 250):
+        lk, hk, xk = _gpu_l1(P, Y, H, lam, 3e-3, L, k, want_x=True)
+        assert lk.tobytes() == log[:k].tobytes(), k
+        figures, failures = K.check_l1_consistency(lk[-1], hk, xk, H, L)
+        print('l1 self-consistency L=%d after %d steps: %s' % (L, k, figures))
+        assert not failures, (k, failures)
+
+
+def test_l1_poisoned_problems_stay_isolated():
+    """A NaN in one problem's Y and an Inf in a pilot matrix that one other problem uses (through p_index): their logs are
+    non-finite from the first step on, and every other problem of the batch of 64 is bit-identical to the clean batch."""
+    B, nch, steps = 64, 8, 40
+    P0, _, H = _data(nch, 38, 71, 10.0)
+    rng = np.random.default_rng(71)
+    idx = np.arange(B) % nch
+    z = (rng.standard_normal((B, 38, 16)) + 1j * rng.standard_normal((B, 38, 16))) / np.sqrt(2)
+    Y = (P0[idx] @ H[idx] + np.sqrt(1.6) * z).astype(np.complex64)
+    P = np.concatenate([P0, P0[3:4]])                          # matrix nch: a copy of matrix 3, used by problem 43 only
+    pidx = idx.copy()
+    pidx[43] = nch
+    lam = np.where(np.arange(B) % 2, 0.3, 0.0)
+    from score_based_channels_amd.baselines import l1_lifted
+
+    def run(Pm, Ym):
+        log, Hh = l1_lifted(torch.from_numpy(Pm).cuda(), torch.from_numpy(Ym).cuda(), torch.from_numpy(H).cuda(), lam, 3e-3, lifting=4,
+                            steps=steps, p_index=pidx, h_index=idx)
+        torch.cuda.synchronize()
+        return log.cpu().numpy(), Hh.cpu().numpy()
+
+    log0, H0 = run(P, Y)
+    assert np.all(np.isfinite(log0))
+    Pp, Yp = P.copy(), Y.copy()
+    Yp[17, 5, 3] = np.nan
+    Pp[nch, 20, 11] = np.inf
+    log1, H1 = run(Pp, Yp)
+    assert not np.any(np.isfinite(log1[:, [17, 43]])), log1[:3, [17, 43]]
+    keep = np.setdiff1d(np.arange(B), [17, 43])
+    assert log1[:, keep].tobytes() == log0[:, keep].tobytes() and H1[keep].tobytes() == H0[keep].tobytes()
+
+
+def _full_run_check(L, npil, seed, snr, lam):
+    B = len(snr)
+    P, Y, H = _data(B, npil, seed, snr)
     log, Hh = _gpu_l1(P, Y, H, lam, 3e-3, L, 1000)
     rlog, rH, _ = O.l1_run(P, Y, H, lam, 3e-3, L, 1000)
     err = np.abs(log / rlog - 1)
+    eH = [np.linalg.norm(Hh[b] - rH[b]) / np.linalg.norm(rH[b]) for b in range(B)]
+    print('l1 full run L=%d Np=%d: log error %.3g (20 steps) %.3g (100) %.3g (1000); H_hat %s'
+          % (L, npil, np.max(err[:20]), np.max(err[:100]), np.max(err), ' '.join('%.2g' % e for e in eH)))
     assert np.max(err[:20]) <= 5e-6, np.max(err[:20])
     assert np.max(err[:100]) <= 2e-4, np.max(err[:100])
     assert np.max(err) <= 5e-3, np.max(err)
@@ -69,8 +141,23 @@ def test_l1_full_run_log_matches_the_oracle(L):
     # drifts along the null space.  The kernel's formulation (G = P^H P, Hz by linearity) restated in numpy complex64 ends
     # 2.0e-3 .. 2.4e-3 from the float64 oracle on these lambda = 0 cells and <= 5.2e-4 on the lambda = 0.3 cells (L = 1 and 4).
     for b in range(B):
-        e = np.linalg.norm(Hh[b] - rH[b]) / np.linalg.norm(rH[b])
-        assert e <= (2e-3 if lam[b] > 0 else 5e-3), (b, lam[b], e)
+        assert eH[b] <= (2e-3 if lam[b] > 0 else 5e-3), (b, lam[b], eH[b])
+
+
+@pytest.mark.parametrize('L', [1, 2, 4])
+def test_l1_full_run_log_matches_the_oracle(L):
+    snrs, lams, per = [-10.0, 10.0, 30.0], [0.0, 0.3], 2
+    cells = [(s, lam) for s in snrs for lam in lams]
+    snr = np.repeat([c[0] for c in cells], per)
+    lam = np.repeat([c[1] for c in cells], per)
+    _full_run_check(L, 38, 21, snr, lam)
+
+
+@pytest.mark.parametrize('npil', [12, 64])
+def test_l1_full_run_at_other_pilot_counts(npil):
+    """1000 steps at the ends of the reference's alpha range (Np = 12: G of rank 12; Np = 64: square), L = 4, the bounds of the
+    Np = 38 run; 4 problems: 10 dB with and without the l1 term, -10 and 30 dB with it."""
+    _full_run_check(4, npil, 200 + npil, np.array([10.0, 10.0, -10.0, 30.0]), np.array([0.0, 0.3, 0.3, 0.3]))
 
 
 def test_l1_threshold_above_the_first_gradient_keeps_x_zero():
@@ -118,8 +205,22 @@ def test_l1_grid_is_batch_independent_and_reproducible():
     assert np.all(np.isfinite(np.delete(log1, 1234, axis=1)))
 
 
-def test_ls_regularized_matches_lstsq():
+def _gpu_ls(P, Y, noise, H=None, **kw):
     from score_based_channels_amd.baselines import ls_regularized
+    Hh, nmse = ls_regularized(torch.from_numpy(P).cuda(), torch.from_numpy(Y).cuda(), noise,
+                              H=torch.from_numpy(H).cuda() if H is not None else None, **kw)
+    torch.cuda.synchronize()
+    return Hh.cpu().numpy(), nmse.cpu().numpy() if nmse is not None else None
+
+
+def _report(tag, figures):
+    for f in figures:
+        print('ML %s s2=%-8.3g kappa %-8.2g H_hat: restatement %.2e kernel %.2e ratio %.2f | residual: %.2e %.2e ratio %.2f | nmse %.2e (bound %.2e)'
+              % (tag, f['noise'], f['kappa'], f['e_c'], f['e_k'], f['e_ratio'], f['r_c'], f['r_k'], f['r_ratio'],
+                 f.get('nmse_err', np.nan), f.get('nmse_bound', np.nan)))
+
+
+def test_ls_regularized_matches_lstsq():
     snr = np.arange(-30, 17.5, 2.5)
     for npil in (38, 64):
         P, _, H = _data(8, npil, 51 + npil, 0.0)
@@ -129,14 +230,68 @@ def test_ls_regularized_matches_lstsq():
         rng = np.random.default_rng(npil)
         z = (rng.standard_normal((B, npil, 16)) + 1j * rng.standard_normal((B, npil, 16))) / np.sqrt(2)
         Y = (P[idx] @ H[idx] + np.sqrt(noise)[:, None, None] * z).astype(np.complex64)
-        Hh, nmse = ls_regularized(torch.from_numpy(P).cuda(), torch.from_numpy(Y).cuda(), noise, H=torch.from_numpy(H).cuda(),
-                                  p_index=idx, h_index=idx)
-        torch.cuda.synchronize()
-        Hh, nmse = Hh.cpu().numpy(), nmse.cpu().numpy()
+        Hh, nmse = _gpu_ls(P, Y, noise, H, p_index=idx, h_index=idx)
         rH, rn = O.lstsq_run(P[idx].astype(np.complex128), Y.astype(np.complex128), H[idx].astype(np.complex128), noise)
         eH = np.linalg.norm((Hh - rH).reshape(B, -1), axis=1) / np.linalg.norm(rH.reshape(B, -1), axis=1)
         assert np.max(eH) <= 1e-4, (npil, np.max(eH))
         assert np.max(np.abs(nmse / rn - 1)) <= 3e-4, (npil, np.max(np.abs(nmse / rn - 1)))
+        # and the conditioning-aware yardstick: 4 x the single-precision restatement per SNR point (cs_checks.check_ls)
+        figures, failures = K.check_ls(Hh, nmse, P[idx], Y, H[idx], noise)
+        _report('CDL-C SNR grid Np=%d' % npil, figures)
+        assert not failures, (npil, failures)
+
+
+@pytest.mark.parametrize('npil,nt,nr', K.LS_GRID)
+def test_ls_geometry_grid(npil, nt, nr):
+    """Every geometry class the header accepts (cs_checks.LS_GRID), 16 problems on 4 pilot matrices and 4 channels through
+    p_index / h_index, noise variances 1e-3, 10^-1.5, 1, 1e3 in one launch, against lstsq in float64 under the bounds of
+    cs_checks.check_ls: 4 x the error and 4 x the residual of the single-precision restatement of the same problems."""
+    P, Y, H, pidx, hidx, noise = K.ls_problem(npil, nt, nr, 1000 + 7 * npil + nt + nr)
+    Hh, nmse = _gpu_ls(P, Y, noise, H, p_index=pidx, h_index=hidx)
+    assert Hh.shape == (16, nt, nr) and nmse.shape == (16,)
+    figures, failures = K.check_ls(Hh, nmse, P[pidx], Y, H[hidx], noise)
+    _report('(%d, %d, %d)' % (npil, nt, nr), figures)
+    assert len(figures) == 4 and not failures, failures
+
+
+def test_ls_on_cdl_channels_with_index_maps():
+    """The grid's bounds on the CDL-C channels of _data(): 16 problems on 4 pilot matrices and 4 channels, Np = 38."""
+    P, _, H = _data(4, 38, 81, 0.0)
+    _, Y, _, pidx, hidx, noise = K.ls_problem(38, 64, 16, 81)
+    rng = np.random.default_rng(82)
+    z = (rng.standard_normal(Y.shape) + 1j * rng.standard_normal(Y.shape)) / np.sqrt(2)
+    Y = (P[pidx] @ H[hidx] + np.sqrt(noise)[:, None, None] * z).astype(np.complex64)
+    Hh, nmse = _gpu_ls(P, Y, noise, H, p_index=pidx, h_index=hidx)
+    figures, failures = K.check_ls(Hh, nmse, P[pidx], Y, H[hidx], noise)
+    _report('CDL-C (38, 64, 16)', figures)
+    assert len(figures) == 4 and not failures, failures
+
+
+@pytest.mark.parametrize('npil,nt,nr', [(38, 64, 16), (12, 64, 16), (100, 33, 5)])
+def test_ls_noise_variance_beyond_the_cli_range(npil, nt, nr):
+    """noise_var is a float32: 1e-6 and 1e6 (the CLI spans 10^-1.5 .. 1e3) under the bounds of the grid.  The system of size
+    min(Np, Nt) has full rank, so a tiny s2 does not make it ill-conditioned."""
+    P, Y, H, pidx, hidx, noise = K.ls_problem(npil, nt, nr, 7 + npil, noises=(1e-6, 1e6))
+    Hh, nmse = _gpu_ls(P, Y, noise, H, p_index=pidx, h_index=hidx)
+    figures, failures = K.check_ls(Hh, nmse, P[pidx], Y, H[hidx], noise)
+    _report('(%d, %d, %d)' % (npil, nt, nr), figures)
+    assert len(figures) == 2 and not failures, failures
+
+
+@pytest.mark.parametrize('npil,nt,nr', [(38, 64, 16), (100, 33, 5)])
+def test_ls_without_h_alone_and_twice(npil, nt, nr):
+    """Bit-identity between launches, for one case of each solution form: without H the estimate is the same and nmse is None;
+    a problem run alone equals its row of the batch; the same batch twice gives the same bits."""
+    P, Y, H, pidx, hidx, noise = K.ls_problem(npil, nt, nr, 90 + npil)
+    Hh, nmse = _gpu_ls(P, Y, noise, H, p_index=pidx, h_index=hidx)
+    H2, n2 = _gpu_ls(P, Y, noise, H, p_index=pidx, h_index=hidx)
+    assert H2.tobytes() == Hh.tobytes() and n2.tobytes() == nmse.tobytes()
+    H3, n3 = _gpu_ls(P, Y, noise, None, p_index=pidx)
+    assert n3 is None and H3.tobytes() == Hh.tobytes()
+    for b in (0, 6, 15):
+        hb, nb = _gpu_ls(P, Y[b:b + 1], noise[b:b + 1], H, p_index=pidx[b:b + 1], h_index=hidx[b:b + 1])
+        assert hb[0].tobytes() == Hh[b].tobytes() and nb.tobytes() == nmse[b:b + 1].tobytes(), b
+    assert np.all(np.isfinite(_ri(Hh))) and np.all(np.isfinite(nmse))
 
 
 def _load(path):
@@ -186,3 +341,47 @@ def test_ml_cli_end_to_end(tmp_path, monkeypatch):
     assert np.max(np.abs(got['oracle_log'] / ref['oracle_log'] - 1)) <= 3e-4
     cli.main(argv)
     assert np.array_equal(_load(path)['oracle_log'], got['oracle_log'])
+
+
+
+@pytest.mark.parametrize('extra,name', [(['--alpha', '0.4', '0.8'], 'l1CS_lifted4'), (['--lifting', '1'], 'l1CS_lifted1')])
+def test_l1_cli_at_other_alphas_and_liftings(tmp_path, monkeypatch, extra, name):
+    """Np = 25 and 51 in one run, and --lifting 1, against the script's restatement; the bounds of test_l1_cli_end_to_end."""
+    from score_based_channels_amd import test_l1Fourier_lifted as cli
+    monkeypatch.chdir(tmp_path)
+    cli.main(['--synthetic', '--seed', '1', '--kept_samples', '3', '--steps', '60', '--no_plot'] + extra)
+    results = tmp_path / 'results'
+    assert [p.name for p in results.iterdir()] == [name]
+    got = _load(results / name / 'train-CDL-C_test-CDL-C' / 'results.pt')
+    kw = dict(alpha=(0.4, 0.8)) if '--alpha' in extra else dict(lifting=1)
+    ref = O.l1_script(seed=1, kept_samples=3, steps=60, **kw)
+    assert set(got) == set(ref) | {'config', 'args'}
+    for k, v in ref.items():
+        assert np.asarray(got[k]).shape == v.shape and np.asarray(got[k]).dtype == v.dtype, k
+    for k in ('snr_range', 'spacing_range', 'alpha_range', 'lmbda_range', 'lr_range', 'best_lmbda', 'best_lr'):
+        assert np.array_equal(got[k], ref[k]), k
+    err = np.abs(got['complete_log'] / ref['complete_log'] - 1)
+    print('l1 CLI %s: log error %.3g (20 steps) %.3g (60)' % (extra, np.max(err[..., :20, :]), np.max(err)))
+    assert np.max(err[..., :20, :]) <= 5e-6 and np.max(err) <= 2e-4, (np.max(err[..., :20, :]), np.max(err))
+    assert np.array_equal(got['nmse_log'], got['complete_log'][..., -1, :])
+    assert np.array_equal(got['best_nmse'], got['nmse_log'].mean(-1)[0, :, 0, 0])
+    assert got['args'].lifting == kw.get('lifting', 4) and got['complete_log'].shape[1] == len(kw.get('alpha', (0.6,)))
+
+
+def test_ml_cli_at_alpha_0p2(tmp_path, monkeypatch):
+    """Np = 12.  The bound is the yardstick of test_ls_geometry_grid carried to the NMSE: at (12, 64, 16) the single-precision
+    restatement is within 2e-7 of lstsq at every noise variance (kappa <= 5), so the kernel within 8e-7; an estimate from 12
+    pilots leaves NMSE >= 0.5 (at most 12 of 64 dimensions are seen), so the propagation factor 2 ||H_ref|| / ||H_ref - H|| is
+    at most 2 sqrt(2) / sqrt(0.5) = 4 and the relative NMSE error at most 3.2e-6 + 2^-23: 1e-5 is asserted."""
+    from score_based_channels_amd import test_ml as cli
+    monkeypatch.chdir(tmp_path)
+    cli.main(['--synthetic', '--seed', '1', '--kept_samples', '3', '--alpha', '0.2'])
+    got = _load(tmp_path / 'results_ml_baseline' / 'model_CDL-D_channel_CDL-D' / 'results_Nt64_Nr16.pt')
+    ref = O.ml_script(seed=1, kept_samples=3, alpha=(0.2,))
+    assert set(got) == set(ref) and got['oracle_log'].shape == (1, 1, 19, 3)
+    assert np.array_equal(got['alpha_range'], ref['alpha_range']) and np.array_equal(got['snr_range'], ref['snr_range'])
+    err = np.max(np.abs(got['oracle_log'] / ref['oracle_log'] - 1))
+    print('ML CLI alpha 0.2: NMSE error %.3g, smallest NMSE %.3g' % (err, ref['oracle_log'].min()))
+    assert ref['oracle_log'].min() >= 0.5
+    assert err <= 1e-5, err
+
