@@ -198,7 +198,7 @@ typedef struct sbc_op {
                                     (uint16).  When set, the convolution runs on the bf16 matrix cores as six bf16
                                     MFMAs per fp32 product block with fp32 accumulation (fp32-level accuracy, see
                                     csrc/conv_x3.hip); takes precedence over `weight_wino` and `weight`, which then
-                                    may be NULL.  SBC_CONV_MODE=f32 in the environment ignores it. */
+                                    may be NULL. */
     const void* weight_wino_split; /* CONV, optional: the Winograd form of a 3x3 weight with every value split into three
                                     bf16 terms, sbc_pack_conv_weight_winograd_split layout [16][cin/16][cout/32][3][64][8]
                                     (uint16): Winograd F(2x2,3x3) with its 16 products on the bf16 matrix cores
@@ -589,22 +589,17 @@ int sbc_ls_regularized(const sbc_ls_desc* desc, void* stream);
 
 /* ---- Environment variables -------------------------------------------------------------------------------------------------
  * Everything the library (csrc/) and the Python host (score_based_channels_amd/) read from the environment, in ONE place.  None of them
- * changes a result: they select between launch plans / kernel variants that compute the same sums (A/B timing aids, each verified
- * bit-identical or within the stated tolerance by tests/), or configure the process (library path, distributed backend).  The
- * torchrun variables RANK / WORLD_SIZE / LOCAL_RANK are read by shard.py.  tests/test_host_logic.py::test_documented_environment_variables
- * holds this list to the getenv / os.environ sites of the tree.
+ * changes a result beyond the stated tolerance of the tests that set them; they configure the process or are needed by a test or by
+ * bench.py.  Kernel selection and launch plans do not depend on the environment otherwise.  The torchrun variables RANK / WORLD_SIZE /
+ * LOCAL_RANK are read by shard.py.  tests/test_host_logic.py::test_documented_environment_variables holds this list to the getenv /
+ * os.environ sites of the tree.
  *
  *   process:    SBC_LIB_PATH (another build of this library), SBC_DIST_BACKEND (nccl | gloo; gloo lets several ranks share one GPU),
  *               SBC_DIST_TIMEOUT_S (bench.py: process-group timeout), SBC_CPU_BASELINE_WORKERS (bench.py: worker count of the cpu_baseline leg)
- *   streams:    SBC_PERSIST_CUS (grid width of the persistent kernels, overrides sbc_plan_set_persistent_cus), SBC_NO_BALANCED_GRID,
- *               SBC_STREAM_SMALL_PX, SBC_STREAM_LAG_MIN_STEPS, SBC_NO_STREAM_LAG, SBC_LAG_RECORDS (driver.run_concurrently / ald.py),
- *               SBC_NO_SKIP_OVERLAP, SBC_SKIP_OVERLAP_MAX_T (scorenet.py: the small-batch plan with the skip branches on a side stream)
- *   plan:       SBC_NO_CONV_DOWN, SBC_NO_CHAIN, SBC_NO_CHAIN4, SBC_NO_CHAIN8, SBC_NO_CHAIN8_CRP, SBC_CHAIN8_RES, SBC_NO_END_SELF,
- *               SBC_NO_RES_BLOCK, SBC_NO_CONV_POOL (plan.py: the unfused record sequence instead of the named fused record),
+ *   tests:      SBC_STREAM_LAG_MIN_STEPS (driver.run_concurrently: fewest steps for which the second stream is lagged),
  *               SBC_NO_CALIB (scorenet.py: f16x2 activation scales stay 1)
- *   kernels:    SBC_NO_PAIR_P3, SBC_NO_PAIR_ROLL, SBC_PAIR_ROLL_MIN_TILES (conv_pair.hip), SBC_DP_WGS, SBC_NO_CONV_DP, SBC_NO_CONV_DP32, SBC_NO_CONV_DP_NORM
- *               (conv_dp.hip), SBC_TILE (conv_x3.hip, conv_mfma.hip), SBC_WX3_MB2 (conv_wx3.hip), SBC_WINO_MB1, SBC_NO_WINO (conv_wino.hip,
- *               conv_mfma.hip), SBC_CONV_MODE=f32, SBC_NO_WX3 (conv_mfma.hip), SBC_CHAIN_NW8, SBC_CHAIN_GD (conv_chain.hip)
+ *   bench.py:   SBC_NO_CONV_DP_NORM (conv_dp.hip: the 64 -> 64 layers with a norm prologue / tile-moment output on the Winograd kernel;
+ *               bench.py names the kernel of its roofline record by it)
  */
 
 #ifdef __cplusplus

@@ -11,7 +11,6 @@ single ``plan.run(n_steps)``: per-step scalars come from device tables indexed b
 NMSE log stays on the device until it is read.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
@@ -203,7 +202,6 @@ class AldBatch:
                 raise RuntimeError('a plan with launch lanes is not cut into a leading and a following part (events would cross the cut)')
             names = [op.name for op in self.bound.plan.ops]
             k = next((i for i, nm in enumerate(names) if nm.startswith('refine31.')), len(names) // 2)
-            k = int(os.environ.get('SBC_LAG_RECORDS', k))        # (A/B aid: where the cut is)
             k = min(max(k, 1), len(self._step_ops) - 1)
             self._lag_plan = _lib.Plan(self._step_ops[:k], keepalive=self)
             self._rest_plan = _lib.Plan(self._step_ops[k:], keepalive=self)
@@ -220,7 +218,7 @@ class AldBatch:
 
     def run_leading(self, n_steps, head_done, width=0):
         """``run(n_steps)`` for the FIRST of two concurrent sub-batch streams: the head of the first step at the process-default grid width
-        (``set_persistent_cus(0)``: every CU unless ``sbc_set_persistent_cus`` / ``SBC_PERSIST_CUS`` say otherwise), then
+        (``set_persistent_cus(0)``: every CU unless ``sbc_set_persistent_cus`` says otherwise), then
         ``head_done()`` (the caller records the event the following stream waits for), then everything else at ``width`` CUs."""
         n = self._check_steps(n_steps)
         head, rest = self._cut_step()
@@ -254,7 +252,7 @@ class AldBatch:
 
     def set_persistent_cus(self, n):
         """Grid width (CUs) of the persistent kernels of THIS batch's launches, 0 = the process default -- all CUs unless
-        ``sbc_set_persistent_cus`` / ``SBC_PERSIST_CUS`` narrowed it (``sbc_plan_set_persistent_cus``: a
+        ``sbc_set_persistent_cus`` narrowed it (``sbc_plan_set_persistent_cus``: a
         field of the batch's plans, not process state -- batches on other threads / streams / devices are unaffected)."""
         self._persist = int(n)
         for pl in (self.plan, self.score_plan, self._lag_plan, self._rest_plan):

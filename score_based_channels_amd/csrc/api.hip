@@ -124,19 +124,17 @@ static std::atomic<int> g_persistent_cus{0};           // sbc_set_persistent_cus
 // two plans driven from two threads, or two handles on two devices, do not see each other's width (ABI 13)
 static thread_local int tls_persistent_cus = 0;
 int persistent_cus(int cus) {
-    static const int env = getenv("SBC_PERSIST_CUS") ? atoi(getenv("SBC_PERSIST_CUS")) : 0;      // A/B aid: overrides the setting
-    const int n = env > 0 ? env : tls_persistent_cus > 0 ? tls_persistent_cus : g_persistent_cus.load(std::memory_order_relaxed);
+    const int n = tls_persistent_cus > 0 ? tls_persistent_cus : g_persistent_cus.load(std::memory_order_relaxed);
     return n > 0 && n < cus ? n : cus;
 }
 // Grid of a persistent kernel whose workgroups take WHOLE samples, one workgroup per CU (conv_res, end_conv_self): the rounds a
 // workgroup makes are an integer, so no more workgroups than that round count needs -- 213 samples on a width of 128 are two
 // rounds either way, 107 workgroups do them and leave 21 CUs to the other stream (425 trajectories per GPU: 1.55 -> 1.47 ms per step).
 // (Taking up to a quarter MORE workgroups than the plan's width where that saves a round -- 850 samples: 142 workgroups, 6 rounds
-// instead of 7 -- was measured too: it costs the other stream what it gains, 4.26 -> 4.29 ms at 1700.)  (A/B aid: SBC_NO_BALANCED_GRID)
+// instead of 7 -- was measured too: it costs the other stream what it gains, 4.26 -> 4.29 ms at 1700.)
 int balanced_sample_grid(int samples, int cus) {
-    static const bool off = getenv("SBC_NO_BALANCED_GRID") != nullptr;
     const int w = persistent_cus(cus);
-    if (off || samples <= 0) return samples < w ? (samples > 0 ? samples : 1) : w;
+    if (samples <= 0) return 1;
     const int rounds = (samples + w - 1) / w;
     return (samples + rounds - 1) / rounds;
 }

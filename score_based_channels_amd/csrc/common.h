@@ -31,8 +31,8 @@ void set_error(const char* fmt, ...);
 // Raise a kernel's dynamic-LDS limit to at least `bytes` on the CURRENT device.  hipFuncSetAttribute is per device, so the
 // high-water mark is cached per (device, kernel) behind a mutex: safe for a process that drives several devices or launches
 // from several host threads (include/sbc_hip.h: threading).  Returns SBC_OK or SBC_ERR_HIP.
-// A/B probe: SBC_PERSIST_CUS=<n> makes the persistent kernels (conv_pair, conv_pool, conv_dp, conv_res) size their grids for n CUs
-// instead of all of them, so that two streams' launches can be resident side by side.
+// sbc_set_persistent_cus / sbc_plan_set_persistent_cus make the persistent kernels (conv_pair, conv_pool, conv_dp, conv_res) size their
+// grids for n CUs instead of all of them, so that two streams' launches can be resident side by side: the width to count on, of `cus`.
 int persistent_cus(int cus);
 int balanced_sample_grid(int samples, int cus);   // grid of the sample-per-workgroup persistent kernels (api.hip)
 int ensure_dyn_lds(const void* kernel, size_t bytes);
@@ -69,7 +69,6 @@ int launch_end_conv_bwd(const sbc_op& op, const sbc_endconv& ext, hipStream_t st
 int launch_begin_conv_bwd(const sbc_op& op, hipStream_t stream);
 int launch_adam_ema(const sbc_op& op, const sbc_adam& ext, hipStream_t stream);
 
-#if defined(__HIPCC__)
 // nn.ELU(alpha=1): x > 0 ? x : exp(x) - 1   (ncsnv2/models/layers.py:12-13).  Written the way PyTorch's own ELU
 // kernels evaluate it, exp(x) - 1, on the hardware exponential (v_exp_f32 of x*log2(e), ~1 ulp) rather than a
 // ~20-instruction expm1: on gfx950 fp32 VALU work and fp32 MFMA share the same ALUs (tools/mfma_valu_coissue.hip:
@@ -148,6 +147,5 @@ __device__ __forceinline__ float4 elu4_acc(float4 v) {
 }
 // `acc` is uniform over the launch: a scalar branch
 __device__ __forceinline__ float4 elu4(float4 v, bool acc) { return acc ? elu4_acc(v) : elu4(v); }
-#endif
 
 }  // namespace sbc

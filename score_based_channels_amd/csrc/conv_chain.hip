@@ -24,7 +24,6 @@
 // The 16 x 4 level (64 channels: refine3 and the low-resolution input of refine4) runs the same kernel with W = 4: a unit is ONE
 // column of ONE sample (its 16 rows; 18 row slots per column), four samples per workgroup, a wave owns all four columns of two
 // samples; the units of column 0 skip the dx = -1 taps and those of column 3 the dx = +1 taps (a sixth of the matrix work).
-#include <stdlib.h>
 #include <string.h>
 #include <type_traits>
 #include "conv_common.h"
@@ -45,17 +44,7 @@ struct ChainParams {
     unsigned* __restrict__ range_flag;
     float* __restrict__ calib;          // sbc_f16x2_calibrate: 3 amax slots per block (inputs of conv 1, conv 2, shortcut conv), else NULL
     int B;
-    unsigned long long* dbg;            // SBC_CHAIN_TIMELINE builds (tools/prof_chain.py): clock stamps of the middle workgroup
 };
-
-#ifdef SBC_CHAIN_TIMELINE
-// the middle workgroup's waves stamp eight points of every phase -> dbg[wave][phase][8]:
-//   0 phase parameters read, 1 operand values formed (ELU / pool / norm), 2 split + filter prologue requested, 3 planes free (barrier),
-//   4 planes written (barrier), 5 K loop done, 6 result taken
-#define CH_T(k) do { if (p.dbg && blockIdx.x == gridDim.x / 2) { const unsigned long long _t = __builtin_readcyclecounter(); if (lane == 0) p.dbg[(wave * 16 + phase_no) * 8 + (k)] = _t; } } while (0)
-#else
-#define CH_T(k) do { } while (0)
-#endif
 
 __device__ __forceinline__ float4 to_f4(f32x4v v) { return make_float4(v[0], v[1], v[2], v[3]); }
 __device__ __forceinline__ f32x4v to_v4(float4 v) { return f32x4v{v.x, v.y, v.z, v.w}; }
@@ -265,8 +254,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_chain_kernel(ChainParams p) {
 
     // phases of a block: every phase is one convolution; what feeds it and what happens to its result depends on the block type
     enum { PH_R1, PH_R2, PH_P1, PH_P2, PH_SC, PH_C1, PH_C2 };
-    int phase_no = -1;
-    (void)phase_no;
 #pragma unroll 1
     for (int blk = 0; blk < p.n_blocks; ++blk) {
         const int type = p.type[blk];
@@ -275,7 +262,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_chain_kernel(ChainParams p) {
         const int dil = p.dil[blk];
 #pragma unroll 1
         for (int ph = 0; ph < n_ph; ++ph) {
-            phase_no = min(phase_no + 1, 15);
             // phase kind and its filter: RCU (conv 1, conv 2), CRP (conv 1, conv 2), RES ([shortcut conv,] conv 1, conv 2)
             const int kind = type == SBC_CHAIN_RCU ? PH_R1 + ph : type == SBC_CHAIN_CRP ? PH_P1 + ph : (has_sc ? PH_SC + ph : PH_C1 + ph);
             const int wi = kind == PH_SC ? 2 : (kind == PH_R2 || kind == PH_P2 || kind == PH_C2) ? 1 : 0;
@@ -291,24 +277,14 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_chain_kernel(ChainParams p) {
             // (ring depth: a K step is NU x 3 matrix instructions long -- with two or four units per wave (the half- and quarter-size
             // groups of small batches, 64 channels at 8 x 2) four steps in flight do not cover the L2 round trip of a filter fragment,
             // and those instantiations have the registers for more)
-#ifndef SBC_CHAIN_WD_SMALL
-#define SBC_CHAIN_WD_SMALL 8
-#endif
-#ifndef SBC_CHAIN_WD_MID
-#define SBC_CHAIN_WD_MID 6
-#endif
-            constexpr int WD = NU <= 2 ? SBC_CHAIN_WD_SMALL : NU <= 4 ? SBC_CHAIN_WD_MID : 4;
+            constexpr int WD = NU <= 2 ? 8 : NU <= 4 ? 6 : 4;
             uint4 wr[WD][2];
             auto ldw = [&](int tap, int kh, int slot) {                 // compile-time constants at every call
-#ifdef SBC_CHAIN_NO_WLOAD   // timing probe (tools/): every K step re-uses the first fragment's registers -- wrong results
-                if (slot != 0) { wr[slot][0] = wr[0][0]; wr[slot][1] = wr[0][1]; return; }
-#endif
                 const int idx = wl_base + ((tap * (C / 16) + 2 * kh) * (C / 32) * 2) * 64;
                 wr[slot][0] = w[idx];
                 wr[slot][1] = w[idx + 64];
             };
 
-            CH_T(0);
             // ---- the operand of this convolution, from registers
             f32x4v v[NU];
             if (kind == PH_R1 || kind == PH_R2) {
@@ -404,13 +380,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_chain_kernel(ChainParams p) {
                     }
                 }
             }
-            CH_T(1);
             float ta = 0.f;
             uint2 vh[NU], vl[NU];
-#ifdef SBC_CHAIN_NO_CONVERT   // timing probe: no ELU / pooling / norm / split (the values above are dead code then) -- wrong results
-#pragma unroll
-            for (int i = 0; i < NU; ++i) { vh[i] = make_uint2(blk, ph); vl[i] = make_uint2(ph, blk); }
-#else
 #pragma unroll
             for (int i = 0; i < NU; ++i) {
                 StageScale ss{scale, ta};
@@ -419,7 +390,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_chain_kernel(ChainParams p) {
                 ta = ss.amax;
                 split_f16x2(f, scale, vh[i], vl[i]);
             }
-#endif
             pair_range_tile(ta, scale, rbits, p.calib ? p.calib + 3 * blk + wi : nullptr);
             // ring position r of the K loop's order: (tap r / KH, slice r % KH); dilated at a width of two: (tap 3 (r / KH) + 1, slice r % KH)
             if (dx0) {
@@ -434,9 +404,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_chain_kernel(ChainParams p) {
                 });
             }
             // every wave has left the previous K loop: the planes may be rewritten
-            CH_T(2);
             lds_barrier();
-            CH_T(3);
 #pragma unroll
             for (int i = 0; i < NU; ++i) {
                 unsigned char* dst = smem + wr_base + (((i / W) * SPU) * SP + (i % W) * CP) * 16;
@@ -444,7 +412,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_chain_kernel(ChainParams p) {
                 *reinterpret_cast<uint2*>(dst + TERM) = vl[i];
             }
             lds_barrier();
-            CH_T(4);
 
             // ---- K loop: D[16 couts][16 pixels] += W[16 couts][32 cin] X[32 cin][16 pixels] per (tap, slice), three fp16 products each.
             // Flat walk over micro-steps m = (K step, pair of units): the four X fragments of a micro-step are requested XD - 1
@@ -459,10 +426,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_chain_kernel(ChainParams p) {
                 const int yy = y + (r - 1) * dil;
                 rb[r] = dil == 1 ? rd_base + r * 16 : ((unsigned)yy < (unsigned)H ? rd_base + (1 + (r - 1) * dil) * 16 : rd_base - y * 16);
             }
-#ifndef SBC_CHAIN_XD
-#define SBC_CHAIN_XD 2
-#endif
-            constexpr int XD = SBC_CHAIN_XD;                            // micro-steps of up to four units: 8 fragments each
+            constexpr int XD = 2;                                       // micro-steps of up to four units: 8 fragments each
             f16x8 xr[XD][8];
             auto kloop = [&](auto dx0c) {
                 constexpr bool DX0 = decltype(dx0c)::value;
@@ -481,9 +445,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_chain_kernel(ChainParams p) {
                 // position of K step s in this loop's filter-ring order
                 auto ring_of = [](int s_) constexpr -> int { return DX0 ? ((s_ / KH) / 3) * KH + s_ % KH : s_; };
                 auto ldx = [&](int m) {
-#ifdef SBC_CHAIN_NO_XLOAD   // timing probe: the operand ring is loaded once -- wrong results
-                    if (m >= XD) return;
-#endif
                     const MicroStep d = step_of(m);
                     const int tap = d.s / KH, kh = d.s % KH, r = tap / 3, dx = tap % 3 - 1;
 #pragma unroll
@@ -531,15 +492,8 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_chain_kernel(ChainParams p) {
                     __builtin_amdgcn_sched_barrier(0);
                 });
             };
-#ifdef SBC_CHAIN_PRIO
-            __builtin_amdgcn_s_setprio(SBC_CHAIN_PRIO);
-#endif
             if (W == 2 && dx0) kloop(std::integral_constant<bool, W == 2>{});
             else kloop(std::false_type{});
-#ifdef SBC_CHAIN_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
-            CH_T(5);
 
             // ---- what the result is for
             if (kind == PH_R2 || kind == PH_P2) {
@@ -557,7 +511,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_chain_kernel(ChainParams p) {
                     for (int e = 0; e < 4; ++e) xs[i][e] = xs[i][e] + fmaf(acc[i][e], descale, b2[e]);
             }
             prev_descale = descale;
-            CH_T(6);
         }
     }
 #pragma unroll
@@ -612,28 +565,23 @@ int launch_chain(const sbc_op& op, const sbc_chain& c, hipStream_t stream, bool 
     }
     p.calib = (float*)op.calib;
     p.B = op.B;
-#ifdef SBC_CHAIN_TIMELINE
-    p.dbg = (unsigned long long*)op.aux;
-#endif
     unsigned* flag = nullptr;
     { const int rc = range_flag_ptr(&flag); if (rc) return rc; }
     p.range_flag = flag;
     // Four-wave workgroups where a 16-output-channel block per wave allows it (64 channels at 8 x 2 / 16 x 4, 32 channels at 32 x 8):
-    // two of them share a CU and drift apart, so one converts operands while the other multiplies (A/B aid: SBC_CHAIN_NW8)
-    static const bool nw8 = getenv("SBC_CHAIN_NW8") != nullptr;
-    if (op.W == 8) return op.cin == 64 ? launch_chain_t<64, 8, 8>(p, stream, dry) : nw8 ? launch_chain_t<32, 8, 8>(p, stream, dry) : launch_chain_t<32, 8, 4>(p, stream, dry);
-    if (op.W == 4) return nw8 ? launch_chain_t<64, 4, 8>(p, stream, dry) : launch_chain_t<64, 4, 4>(p, stream, dry);
+    // two of them share a CU and drift apart, so one converts operands while the other multiplies
+    if (op.W == 8) return op.cin == 64 ? launch_chain_t<64, 8, 8>(p, stream, dry) : launch_chain_t<32, 8, 4>(p, stream, dry);
+    if (op.W == 4) return launch_chain_t<64, 4, 4>(p, stream, dry);
     // 8 x 2 samples, small batches: half groups when the full groups would occupy at most half of the CUs this launch may count on
-    // (the plan's persistent-grid width: all CUs, or half of them when two sub-batch streams share the chip).  (A/B aid: SBC_CHAIN_GD=1 / 2)
+    // (the plan's persistent-grid width: all CUs, or half of them when two sub-batch streams share the chip).
     int dev = 0, cus = 256;
     SBC_CHECK_HIP(hipGetDevice(&dev));
     SBC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    static const int force_gd = getenv("SBC_CHAIN_GD") ? atoi(getenv("SBC_CHAIN_GD")) : 0;
     const int avail = persistent_cus(cus);
     if (op.cin == 128) {
-        const bool half = force_gd ? force_gd == 2 : 2 * ((op.B + 7) / 8) <= avail;
+        const bool half = 2 * ((op.B + 7) / 8) <= avail;
         // quarter groups while they occupy at most half of the CUs (213 samples: 107 workgroups, -2 % per step; 425 samples: 213 workgroups, +3 %: half groups)
-        const bool quarter = force_gd ? force_gd == 4 : (op.B + 1) / 2 <= avail / 2;
+        const bool quarter = (op.B + 1) / 2 <= avail / 2;
         if (dry) {
             int rc = launch_chain_t<128, 2, 8, 4>(p, stream, true);
             if (!rc) rc = launch_chain_t<128, 2, 8, 2>(p, stream, true);
@@ -641,8 +589,7 @@ int launch_chain(const sbc_op& op, const sbc_chain& c, hipStream_t stream, bool 
         }
         return quarter ? launch_chain_t<128, 2, 8, 4>(p, stream, dry) : half ? launch_chain_t<128, 2, 8, 2>(p, stream, dry) : launch_chain_t<128, 2, 8>(p, stream, dry);
     }
-    if (nw8) return launch_chain_t<64, 2, 8>(p, stream, dry);
-    const bool half = force_gd ? force_gd == 2 : 2 * ((op.B + 3) / 4) <= 2 * avail;      // (two 4-wave workgroups per CU)
+    const bool half = 2 * ((op.B + 3) / 4) <= 2 * avail;      // (two 4-wave workgroups per CU)
     if (dry) { const int rc = launch_chain_t<64, 2, 4, 2>(p, stream, true); if (rc) return rc; return launch_chain_t<64, 2, 4>(p, stream, true); }
     return half ? launch_chain_t<64, 2, 4, 2>(p, stream, dry) : launch_chain_t<64, 2, 4>(p, stream, dry);
 }

@@ -34,14 +34,11 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "conv_common.h"
-#ifndef DP_RING
-#define DP_RING 3      // operand ring depth of the K loop (4 and 5 measured: no gain)
-#endif
-#ifndef DP_SETPRIO
-#define DP_SETPRIO 3   // wave priority inside the K loop (88.2 us against 90.8 without at 1700 x 32 x 8)
-#endif
 
 namespace sbc {
+
+constexpr int DP_RING = 3;      // operand ring depth of the K loop (4 and 5 measured: no gain)
+constexpr int DP_SETPRIO = 3;   // wave priority inside the K loop (88.2 us against 90.8 without at 1700 x 32 x 8)
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
@@ -67,14 +64,7 @@ struct DpParams {
     float* __restrict__ calib;          // sbc_f16x2_calibrate: amax slot of the input, else NULL
     int flags;                          // SBC_PRO_ELU, SBC_EPI_RES1_ELU
     int B, H, ntiles, tiles_per_sample, wgs_per_xcd, tiles_per_xcd;
-    unsigned long long* dbg;            // SBC_PAIR_TIMING builds: per-phase cycle sums of wave 0 of every workgroup
 };
-
-#ifdef SBC_PAIR_TIMING
-#define DP_MARK(k) do { const unsigned long long _t = __builtin_readcyclecounter(); pt[k] += _t - pt_last; pt_last = _t; } while (0)
-#else
-#define DP_MARK(k) do { } while (0)
-#endif
 
 // FULL: a tile is S whole samples (R = H): no halo rows are fetched, the plane rows above and below a sample stay zero.
 // C = 32: eight waves (two output-channel groups x four unit groups, 128 registers a wave: the fragments are 72), still two
@@ -177,9 +167,6 @@ __global__ __launch_bounds__(64 * NW, (C == 32 ? 3 : 2) * NW / 4) void conv_dp_k
     };
     int tile = t_begin + jw * GS;
     if (tile < t_end) issue_dma(tile);
-#ifdef SBC_PAIR_TIMING
-    unsigned long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pt_last = __builtin_readcyclecounter();
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                          // first tile (and the filter fragments) landed
 
     for (; tile < t_end; tile = next_tile(tile)) {
@@ -195,9 +182,7 @@ __global__ __launch_bounds__(64 * NW, (C == 32 ? 3 : 2) * NW / 4) void conv_dp_k
             nmu = *reinterpret_cast<const float4*>(st); nsc = *reinterpret_cast<const float4*>(st + C); nsh = *reinterpret_cast<const float4*>(st + 2 * C);
         }
         // (1) raw tile landed, for every wave; and every wave is through the previous tile's K loop (the planes are free)
-        DP_MARK(0);
         asm volatile("s_barrier" ::: "memory");
-        DP_MARK(1);
         // (2) convert raw -> operand planes: all of the lane's raw chunks first (one LDS round trip), then straight-line arithmetic --
         // one copy of the loop per ELU form, so that nothing branches between the chunks
         float ta = 0.f;
@@ -254,9 +239,7 @@ __global__ __launch_bounds__(64 * NW, (C == 32 ? 3 : 2) * NW / 4) void conv_dp_k
         else if (!elu_acc) convert(std::integral_constant<int, 1>{});
         else convert(std::integral_constant<int, 2>{});
         pair_range_tile(ta, scale, rbits, p.calib);
-        DP_MARK(2);
         lds_barrier();
-        DP_MARK(3);
         // the raw copy is consumed: request the next tile of this workgroup; it flies during the K loop
         if (next_tile(tile) < t_end) issue_dma(next_tile(tile));
 
@@ -296,9 +279,7 @@ __global__ __launch_bounds__(64 * NW, (C == 32 ? 3 : 2) * NW / 4) void conv_dp_k
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const int tap = s / (KH * NU), kh = (s / NU) % KH, i = s % NU;
-#ifndef DP_PROBE_NOLDS      // timing probe (wrong results): the K loop without its LDS reads
                 if (s + D - 1 < NS) ld(s + D - 1);
-#endif
                 const f16x8 xh = ring[s % D][0], xl = ring[s % D][1];
                 const f16x8 wh = __builtin_bit_cast(f16x8, wf[tap][kh][0]), wl = __builtin_bit_cast(f16x8, wf[tap][kh][1]);
                 const f32x4v c0 = (tap == 0 && kh == 0) ? f32x4v{0.f, 0.f, 0.f, 0.f} : acc[i];
@@ -309,7 +290,6 @@ __global__ __launch_bounds__(64 * NW, (C == 32 ? 3 : 2) * NW / 4) void conv_dp_k
             }
         }
         __builtin_amdgcn_s_setprio(0);
-        DP_MARK(4);
         float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
         if (p.bias) {
             int cqo = cq;
@@ -329,7 +309,6 @@ __global__ __launch_bounds__(64 * NW, (C == 32 ? 3 : 2) * NW / 4) void conv_dp_k
         }
         // everything this wave has in flight -- the residuals, its pieces of the next tile's DMA -- has landed
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        DP_MARK(5);
         float4 ysum = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int i = 0; i < NU; ++i) {
@@ -343,9 +322,6 @@ __global__ __launch_bounds__(64 * NW, (C == 32 ? 3 : 2) * NW / 4) void conv_dp_k
                 if (!NM && p.res2) { rr.x = x2[i].x + rr.x; rr.y = x2[i].y + rr.y; rr.z = x2[i].z + rr.z; rr.w = x2[i].w + rr.w; }
                 y.x += rr.x; y.y += rr.y; y.z += rr.z; y.w += rr.w;
             }
-#ifdef DP_PROBE_NOSTORE   // timing probe (wrong results): everything but the output stores
-            if (y.x == 123456.f)
-#endif
             st_out(p.out + o0 + DO(i), y);
             if (NM && p.pm_out) { acc[i] = f32x4v{y.x, y.y, y.z, y.w}; ysum.x += y.x; ysum.y += y.y; ysum.z += y.z; ysum.w += y.w; }
         }
@@ -380,14 +356,8 @@ __global__ __launch_bounds__(64 * NW, (C == 32 ? 3 : 2) * NW / 4) void conv_dp_k
                 }
             }
         }
-        DP_MARK(6);
     }
     if (rbits && lane == 0) atomicOr(p.range_flag, rbits);
-#ifdef SBC_PAIR_TIMING
-    // [wait for the raw tile, barrier, convert, barrier, dma issue + residual requests + K loop, load wait, store]
-    if (tid == 0 && p.dbg)
-        for (int k = 0; k < 7; ++k) atomicAdd(p.dbg + k, pt[k]);
-#endif
 }
 
 template <int C, int W, int R, int S, bool FULL, int NW, bool NM = false>
@@ -409,9 +379,6 @@ static int launch_dp(const DpParams& p0, hipStream_t stream, bool dry) {
     const int gs = p.pm_out ? 2 : 1;                                       // tiles a workgroup takes back to back (conv_dp_kernel: GS)
     p.tiles_per_xcd = ((p.ntiles + 8 * gs - 1) / (8 * gs)) * gs;
     p.wgs_per_xcd = max(1, min(WGPC * persistent_cus(cus) / 8, (p.tiles_per_xcd + gs - 1) / gs));
-#ifdef SBC_PAIR_TIMING
-    if (getenv("SBC_DP_WGS")) p.wgs_per_xcd = max(1, min(atoi(getenv("SBC_DP_WGS")), p.tiles_per_xcd));   // probe: workgroups per XCD
-#endif
     hipLaunchKernelGGL(kern, dim3(8 * p.wgs_per_xcd), dim3(64 * NW), lds, stream, p);
     SBC_CHECK_HIP(hipGetLastError());
     return SBC_OK;
@@ -419,10 +386,8 @@ static int launch_dp(const DpParams& p0, hipStream_t stream, bool dry) {
 
 // 1: not this kernel's layer (the caller goes on to the Winograd kernel); 0: launched; < 0: error
 int launch_conv_dp(const sbc_op& op, unsigned* range_flag, hipStream_t stream, bool dry) {
-    static const bool off = getenv("SBC_NO_CONV_DP") != nullptr;             // A/B aid
-    static const bool off32 = getenv("SBC_NO_CONV_DP32") != nullptr;         // A/B aid: 32-channel layers only
-    if (off || !(op.flags & SBC_CONV_F16X2) || !op.weight_split || op.cin != op.cout || op.ksize != 3 || op.dil != 1) return 1;
-    if (op.cin != 64 && (op.cin != 32 || off32)) return 1;
+    if (!(op.flags & SBC_CONV_F16X2) || !op.weight_split || op.cin != op.cout || op.ksize != 3 || op.dil != 1) return 1;
+    if (op.cin != 64 && op.cin != 32) return 1;
     if (op.flags & (SBC_EPI_POOL | SBC_EPI_UP | SBC_EPI_ELUGRAD | SBC_PRO_NORM_SELF)) return 1;
     if (op.res2 && !op.res1) return 1;
     // a norm prologue / a tile-moment output: the 64-channel kernel at 8-pixel rows only (round 6; moment tiles are 16 rows)
@@ -441,7 +406,6 @@ int launch_conv_dp(const sbc_op& op, unsigned* range_flag, hipStream_t stream, b
     p.stats = (op.flags & SBC_PRO_NORM) ? (const float*)op.stats : nullptr;
     p.pm_out = (op.flags & SBC_EPI_MOMENTS_OUT) ? (float*)op.aux : nullptr;
     p.range_flag = range_flag; p.calib = (float*)op.calib;
-    p.dbg = (op.flags & SBC_EPI_MOMENTS_OUT) ? nullptr : (unsigned long long*)op.aux;
     if (op.cin == 32) return w16 ? launch_dp<32, 16, 8, 1, false, 4>(p, stream, dry) : launch_dp<32, 8, 8, 1, false, 4>(p, stream, dry);
     if (w8 && (p.stats || p.pm_out)) return launch_dp<64, 8, 8, 1, false, 4, true>(p, stream, dry);
     if (w8) return launch_dp<64, 8, 8, 1, false, 4>(p, stream, dry);

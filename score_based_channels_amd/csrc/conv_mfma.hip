@@ -24,8 +24,6 @@
 //
 // Experiments around this kernel that did not pay off (persistent workgroups, weights in LDS, staggering, ...) are
 // recorded in DESIGN.md section 5.
-#include <stdlib.h>
-#include <string.h>
 #include "conv_epilogue.h"
 
 namespace sbc {
@@ -199,10 +197,8 @@ static int launch_sized(const ConvParams& p, hipStream_t stream, bool dry) {
     auto fits = [&](int tm) {
         return tm % p.W == 0 && (HW % tm == 0 || tm % HW == 0) && (!(p.flags & SBC_EPI_POOL) || tm % (2 * p.W) == 0);
     };
-    static const int force = getenv("SBC_TILE") ? atoi(getenv("SBC_TILE")) : 0;     // tuning aid
     int tm = 0;
-    if (force && fits(force)) tm = force;
-    else if (fits(256) && px >= 256L * 512) tm = 256;
+    if (fits(256) && px >= 256L * 512) tm = 256;
     else if (fits(128) && px >= 128L * 512) tm = 128;
     else if (fits(64)) tm = 64;
     else if (fits(128)) tm = 128;
@@ -222,8 +218,7 @@ static int launch_sized(const ConvParams& p, hipStream_t stream, bool dry) {
 // dry = true: resolve the kernel variant and set its function attributes without launching (done at plan creation
 // so that nothing but kernel launches happens inside a hipGraph capture)
 int launch_conv(const sbc_op& op, hipStream_t stream, bool dry) {
-    static const bool f32_only = getenv("SBC_CONV_MODE") && !strcmp(getenv("SBC_CONV_MODE"), "f32");   // A/B aid
-    const bool x3 = op.weight_split && !f32_only;
+    const bool x3 = op.weight_split != nullptr;
     SBC_REQUIRE(op.in && op.out && (op.weight || x3), "conv: in/out/weight must be set");
     SBC_REQUIRE(op.B > 0 && op.H > 0 && op.W > 0, "conv: bad shape B=%d H=%d W=%d", op.B, op.H, op.W);
     SBC_REQUIRE(op.ksize == 1 || op.ksize == 3, "conv: ksize %d (only 1 and 3)", op.ksize);
@@ -269,14 +264,13 @@ int launch_conv(const sbc_op& op, hipStream_t stream, bool dry) {
     SBC_REQUIRE(!(op.flags & SBC_PRO_NORM_MOMENTS), "conv: SBC_PRO_NORM_MOMENTS belongs to SBC_OP_INORM_STATS (statistics from tile moments)");
     if (op.flags & SBC_PRO_NORM_SELF) {
         const int hw = op.H * op.W;
-        SBC_REQUIRE((op.flags & SBC_PRO_NORM) && (x3 || (op.weight_wino_split && !f32_only)) && op.ksize == 3 && hw <= 64 && !(hw & (hw - 1)) && p.hsh >= 0 && p.wsh >= 1 &&
+        SBC_REQUIRE((op.flags & SBC_PRO_NORM) && (x3 || op.weight_wino_split) && op.ksize == 3 && hw <= 64 && !(hw & (hw - 1)) && p.hsh >= 0 && p.wsh >= 1 &&
                     !(op.flags & SBC_EPI_ELUGRAD),
                     "conv: SBC_PRO_NORM_SELF needs SBC_PRO_NORM, a matrix-core weight form (weight_split), a 3x3 kernel and a "
                     "power-of-two image of at most 64 pixels (got %dx%d, ksize %d)", op.H, op.W, op.ksize);
     }
-    static const bool no_wx3 = getenv("SBC_NO_WX3") != nullptr;                    // A/B aid: direct split-bf16 kernel everywhere
     const bool direct_only = (op.flags & SBC_EPI_ELUGRAD) != 0;       // the fp32 Winograd kernel's epilogue does not know the flag
-    if ((op.flags & SBC_CONV_F16X2) && !f32_only) {
+    if (op.flags & SBC_CONV_F16X2) {
         const int rc = launch_conv_dp(op, p.range_flag, stream, dry);
         if (rc <= 0) return rc;                                                    // launched (0) or failed (< 0)
     }
@@ -285,15 +279,9 @@ int launch_conv(const sbc_op& op, hipStream_t stream, bool dry) {
     // 1291 us, 64 -> 64 174 / 199, 128 -> 128 158 / 279, pooled 32 -> 64 1684 / 2143.  The direct kernel takes every f16w layer except
     // the 64-channel producers of tile moments (its epilogue writes moments for 32 output channels only).
     const bool f16w_direct = (op.flags & SBC_CONV_F16W) && x3 && !(moments && op.cout != 32);
-    if (op.weight_wino_split && !f32_only && !no_wx3 && !f16w_direct && op.ksize == 3 && op.dil == 1) {
+    if (op.weight_wino_split && !f16w_direct && op.ksize == 3 && op.dil == 1) {
         ConvParams pw = p;
         pw.wpk = (const float4*)op.weight_wino_split;
-#ifdef SBC_WITH_WP   // tools/experiments/conv_wp.hip (round 4: 64 -> 64 with the transformed filter resident in registers; measured slower)
-        {
-            const int rc = launch_conv_wp(pw, op.cin, op.cout, stream, dry);
-            if (rc <= 0) return rc;
-        }
-#endif
         const int rc = launch_conv_wx3(pw, op.cin, op.cout, stream, dry);
         if (rc <= 0) return rc;                                                    // launched (0) or failed (< 0)
     }
@@ -308,8 +296,7 @@ int launch_conv(const sbc_op& op, hipStream_t stream, bool dry) {
     }
     SBC_REQUIRE(!(op.flags & SBC_PRO_NORM_SELF), "conv: SBC_PRO_NORM_SELF: no matrix-core kernel takes this layer (%dx%d, %d -> %d, dilation %d)",
                 op.H, op.W, op.cin, op.cout, op.dil);
-    static const bool no_wino = getenv("SBC_NO_WINO") != nullptr;                  // A/B aid
-    if (op.weight_wino && op.ksize == 3 && op.dil == 1 && !no_wino && !direct_only) {
+    if (op.weight_wino && op.ksize == 3 && op.dil == 1 && !direct_only) {
         ConvParams pw = p;
         pw.wpk = (const float4*)op.weight_wino;
         const int rc = launch_conv_wino(pw, op.cin, op.cout, stream, dry);

@@ -15,11 +15,6 @@ struct PairParams {
     const float* __restrict__ res2;
     int flags;                          // conv_pool_kernel: SBC_PRO_ELU, SBC_EPI_RES1_ELU
     int B, H, ntiles, tiles_per_sample, wgs_per_xcd, tiles_per_xcd;
-    unsigned long long* dbg;            // SBC_PAIR_TIMING builds: per-phase cycle sums of wave 0 of every workgroup
 };
-
-// (tools/experiments/conv_pair32.hip -- the RCU block on v_mfma_f32_32x32x16_f16 with the vector work between the matrix instructions,
-// round 6: correct, slower; DESIGN.md section 9 -- declares its launcher against this struct)
-int launch_pair32(const PairParams& p0, hipStream_t stream, bool dry);
 
 }  // namespace sbc

@@ -17,19 +17,12 @@
 //   5. conv2 the same way on the R output rows; its epilogue adds the residual x (re-read from L2, fp32) and stores float4s.
 // A 16 x 16 unit is one image row (W = 16), two rows (W = 8) or part of a row (W >= 32); wave w owns output-channel half w & 1
 // and every second unit, so with R = 8 at W = 16 the four waves run 5 + 4 units each: no idle wave in either convolution.
-#include <stdlib.h>
 #include <type_traits>
 #include "conv_pair.h"
 
 namespace sbc {
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-#ifdef SBC_PAIR_TIMING
-#define PT_MARK(k) do { const unsigned long long _t = __builtin_readcyclecounter(); pt[k] += _t - pt_last; pt_last = _t; } while (0)
-#else
-#define PT_MARK(k) do { } while (0)
-#endif
 
 // NW waves per workgroup: 4 (two workgroups per CU) for images 8 / 16 pixels wide; 8 (one workgroup per CU, its LDS) for 64-pixel
 // rows, where wave pair `sub` owns column block `sub` of every row of the tile.
@@ -140,17 +133,12 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_pair_kernel(PairParams p) {
     };
     int tile = t_begin + jw;
     if (tile < t_end) issue_dma(tile);
-#ifdef SBC_PAIR_TIMING
-    unsigned long long pt[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pt_last = __builtin_readcyclecounter();
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // first tile (and the filter fragments) landed
 
     for (; tile < t_end; tile += p.wgs_per_xcd) {
         const int n = tile / p.tiles_per_sample, r0 = (tile - n * p.tiles_per_sample) * R;
         // (1) raw tile landed, for every wave (each wave waited for its own pieces before its previous epilogue / the loop)
-        PT_MARK(0);
         asm volatile("s_barrier" ::: "memory");
-        PT_MARK(1);
         // (2) convert raw -> operand planes of conv1
         float ta = 0.f, tb = 0.f;
 #pragma unroll
@@ -178,12 +166,9 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_pair_kernel(PairParams p) {
             }
         }
         if constexpr (MODE == 2) pair_range_tile(ta, scale1, rbits, p.calib);
-        PT_MARK(2);
         lds_barrier();
-        PT_MARK(3);
         // the raw copy is consumed: request the next tile of this workgroup; it flies during both K loops
         if (tile + p.wgs_per_xcd < t_end) issue_dma(tile + p.wgs_per_xcd);
-        PT_MARK(8);
 
         // one convolution over units `sub`, `sub + 2`, ...: acc[i] = D[16 couts of this wave][16 pixels of unit i]
         auto conv = [&](auto cvc, const int plane_off, const int PS, auto nuc, auto nutc, f32x4v* acc) {
@@ -233,7 +218,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_pair_kernel(PairParams p) {
         {
             f32x4v acc[NU1];
             conv(std::integral_constant<int, 0>{}, X_OFF, XPS, std::integral_constant<int, NU1>{}, std::integral_constant<int, NU1T>{}, acc);
-            PT_MARK(9);
             const int cq = 4 * hf + kq;                                    // channel quad of this lane's four outputs
 #pragma unroll
             for (int i = 0; i < NU1; ++i) {
@@ -261,9 +245,7 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_pair_kernel(PairParams p) {
             }
         }
         if constexpr (MODE == 2) pair_range_tile(tb, scale2, rbits, p.calib ? p.calib + 1 : nullptr);
-        PT_MARK(4);
         lds_barrier();
-        PT_MARK(5);
         // (4) conv2 on the R output rows, + residual, store
         {
             f32x4v acc[NU2];
@@ -276,7 +258,6 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_pair_kernel(PairParams p) {
             for (int i = 0; i < NU2; ++i)
                 if (NU2T % USTEP == 0 || u0 + USTEP * i < NU2T) xr[i] = *reinterpret_cast<const float4*>(p.in + o0 + i * DO);
             conv(std::integral_constant<int, 1>{}, M_OFF, MPS, std::integral_constant<int, NU2>{}, std::integral_constant<int, NU2T>{}, acc);
-            PT_MARK(6);
             // everything this wave has in flight -- the residual, its pieces of the next tile's DMA -- has landed; the stores below
             // are never waited for explicitly (the same wait one iteration later covers them)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -289,306 +270,24 @@ __global__ __launch_bounds__(64 * NW, 2) void conv_pair_kernel(PairParams p) {
                     st_out(p.out + o0 + i * DO, y);
                 }
             }
-            PT_MARK(7);
         }
         // the next iteration's barrier (1) orders conv2's reads of the intermediate planes before anything rewrites them
     }
     if constexpr (MODE == 2) {
         if (rbits && (threadIdx.x & 63) == 0) atomicOr(p.range_flag, rbits);
     }
-#ifdef SBC_PAIR_TIMING
-    if (tid == 0 && p.dbg)
-        for (int k = 0; k < 10; ++k) atomicAdd(p.dbg + k, pt[k]);
-#endif
 }
 
-// The same block as a three-stage pipeline over tiles (P3): one persistent workgroup per CU of 3 NW waves in three roles --
-//   role 2 (conversion): keeps one tile of LDS-DMA in flight and turns the raw copy of tile i into operand planes X[i & 1];
-//   role 0 (conv1):      K loop of conv1 on X[(i-1) & 1], ELU, split -> intermediate planes M[(i-1) & 1];
-//   role 1 (conv2):      K loop of conv2 on M[(i-2) & 1], + x, store.
-// Every buffer is double buffered, so one workgroup barrier per tile is all the synchronisation there is; each role keeps only its
-// own filter fragments (72 registers in f16x2), which is what lets three waves share a SIMD (168 registers each): two of them are
-// always inside a K loop while the third does the vector-ALU work.  Same arithmetic in the same order as conv_pair_kernel: the
-// outputs are identical bit for bit.  13 600 tiles: 180 us in the network against 203 (matrix pipe 0.57 busy against 0.51).
-// (Two roles -- four matrix waves that keep both convolutions' fragments, four conversion waves -- were slower than the
-// two-workgroup kernel above, 256 us against 244 back to back: ONE matrix wave per SIMD does not keep the matrix pipe fed.  The same
-// holds inside the pipeline: matrix waves that own all 32 output channels of their units -- half the LDS reads, two waves per
-// matrix role -- run 279 us against 231.)
-template <int W, int R, int MODE, int NW = 4, int C = 32>
-__global__ __launch_bounds__(192 * NW, 3) void conv_pair_p3_kernel(PairParams p) {
-    constexpr int NTH = 64 * NW, NHF = C / 16, NSUB = NW / NHF;
-    constexpr int KGS = C / 8, KH = C / 32, C4 = C / 4;   // 8-channel plane groups, 32-channel halves of the contraction, channel quads
-    static_assert(C == 32 || (C == 64 && MODE == 1), "64 channels: fp16-weight mode only (filter fragments must fit in registers)");
-    constexpr int NT = MODE == 2 ? 2 : 1;            // fp16 terms per operand
-    constexpr int RI = R + 4, RM = R + 2;             // staged input rows, intermediate rows
-    constexpr int WP = W + 2;                         // row of a plane: zero pixel, W pixels, zero pixel
-    constexpr int XPS = (RI * WP * 16 + 255) / 256 * 256;     // bytes of one k-group plane (multiple of the 256-byte bank row)
-    constexpr int MPS = (RM * WP * 16 + 255) / 256 * 256;
-    constexpr int RAW_BYTES = RI * W * C * 4;
-    constexpr int XSZ = NT * KGS * XPS;                 // one set of input planes
-    constexpr int MSZ = NT * KGS * MPS;                 // one set of intermediate planes
-    constexpr int X_OFF = 2 * RAW_BYTES, M_OFF = X_OFF + 2 * XSZ;
-    constexpr int NQ = RI * W * C4;                   // 16-byte chunks of the raw tile
-    static_assert(NQ % NTH == 0, "raw tile must divide over the workgroup's threads");
-    constexpr int CB = W >= 16 ? W / 16 : 1;          // units per image row (W >= 16)
-    constexpr int RPU = W >= 16 ? 1 : 16 / W;         // image rows per unit (W < 16)
-    constexpr bool COLS = CB > 1;                     // wide rows: wave pair `sub` owns column block `sub`, unit i = row i
-    static_assert(!COLS || CB == NSUB, "one wave pair per column block");
-    constexpr int NU1T = COLS ? RM : RM * W / 16, NU2T = COLS ? R : R * W / 16;   // units per output-channel half (and column block)
-    constexpr int USTEP = COLS ? 1 : NSUB;            // unit index step between a wave's consecutive units
-    constexpr int NU1 = (NU1T + USTEP - 1) / USTEP, NU2 = (NU2T + USTEP - 1) / USTEP;  // per wave
-    static_assert(RM % RPU == 0 && R % RPU == 0, "units must not straddle the tile");
-    extern __shared__ __attribute__((aligned(256))) unsigned char smem[];
-
-    const int role = __builtin_amdgcn_readfirstlane((int)threadIdx.x / NTH);      // 0: conv1 waves, 1: conv2 waves, 2: conversion waves
-    const int tid = threadIdx.x - role * NTH, lane = tid & 63;                   // (role-local)
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int hf = wave % NHF, sub = wave / NHF;      // 16-output-channel group; unit parity / column block of this wave
-    const int kq = lane >> 4, c = lane & 15;          // k-group (8 input channels) / pixel of the unit
-    const int H = p.H;
-    // unit i of this wave: first plane row and slot column of its 16 pixels (this lane: pixel c), and the step to unit i + 1
-    const int u0 = COLS ? 0 : sub;
-    const int urow0 = u0 * RPU + (W >= 16 ? 0 : c / W);
-    const int ucol = COLS ? sub * 16 + c : (W >= 16 ? c : c % W);
-    constexpr int UROWS = USTEP * RPU;                 // image rows from a wave's unit i to its unit i + 1
-
-    // ---- filter fragments of THIS ROLE's convolution, resident for the whole launch (A operand: lane = cout l & 15, k-group l >> 4)
-    // (packed layout [tap][C/16 input groups g][C/32 output blocks nb][terms][64 lanes]: lane l' = cout % 32 + 32 * (cin group half))
-    uint4 wf[9][KH][NT];
-    if (role < 2) {
-        const int lsrc = (16 * (hf & 1) + c) + 32 * (kq & 1), nb = hf >> 1;
-        const uint4* w = role == 0 ? p.w1 : p.w2;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-            for (int kh = 0; kh < KH; ++kh)
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    wf[tap][kh][t] = w[(((tap * (C / 16) + 2 * kh + (kq >> 1)) * (C / 32) + nb) * NT + t) * 64 + lsrc];
-    }
-    float scale1 = 1.f, descale1 = 1.f, scale2 = 1.f, descale2 = 1.f;
-    // range tracking (tile.h): per tile, max |x| of what this lane converts for conv1 (ta) / writes as the intermediate (tb); the
-    // wave-level verdicts accumulate in `rbits`
-    unsigned rbits = 0;
-    if constexpr (MODE == 2) {
-        const float4 t1 = f16x2_trailer(reinterpret_cast<const float4*>(p.w1), 9 * (C / 16) * (C / 32) * NT);
-        const float4 t2 = f16x2_trailer(reinterpret_cast<const float4*>(p.w2), 9 * (C / 16) * (C / 32) * NT);
-        scale1 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t1.x)));
-        scale2 = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t2.x)));
-        descale1 = t1.y; descale2 = t2.y;
-        // the calibration found one of the two convolutions' inputs below 2^-4 (fourth trailer word): this kernel evaluates ELU as
-        // exp(x) - 1 only (it has no registers for the accurate form of common.h) -- say so, the host re-runs the batch in bf16x3
-        if (t1.w != 0.f || t2.w != 0.f) rbits |= 4u;
-    }
-
-    // ---- zero the padding columns of every plane once (nothing writes them afterwards)
-    for (int i = threadIdx.x; i < 2 * NT * KGS * RI * 2; i += 3 * NTH) {              // (the two sets are contiguous)
-        const int side = i & 1, row = (i >> 1) % RI, pl = (i >> 1) / RI;
-        *reinterpret_cast<uint4*>(smem + X_OFF + pl * XPS + (row * WP + side * (W + 1)) * 16) = make_uint4(0, 0, 0, 0);
-    }
-    for (int i = threadIdx.x; i < 2 * NT * KGS * RM * 2; i += 3 * NTH) {                      // (two contiguous sets)
-        const int side = i & 1, row = (i >> 1) % RM, pl = (i >> 1) / RM;
-        *reinterpret_cast<uint4*>(smem + M_OFF + pl * MPS + (row * WP + side * (W + 1)) * 16) = make_uint4(0, 0, 0, 0);
-    }
-
-    // ---- tile walk: XCD x (= blockIdx % 8) owns a contiguous run of tiles, its workgroups take consecutive tiles of it
-    const int xcd = blockIdx.x & 7, jw = blockIdx.x >> 3;
-    const int t_begin = xcd * p.tiles_per_xcd;
-    const int t_end = min(t_begin + p.tiles_per_xcd, p.ntiles);
-    auto issue_dma = [&](int tile, int buf) {
-        const int n = tile / p.tiles_per_sample, r0 = (tile - n * p.tiles_per_sample) * R;
-#pragma unroll
-        for (int k = 0; k < NQ / NTH; ++k) {
-            const int j = k * NW + wave;                                  // wave-instruction: chunks j * 64 .. + 63
-            const int ri = (j * 64) / (W * C4), within = j * 64 - ri * (W * C4);   // its (single) tile row, first chunk in the row
-            // rows outside the sample are requested from the nearest row inside it (the conversion writes zeros for them): no
-            // branch around a request, every wave issues exactly NQ / NTH of them per tile
-            const int grow = min(max(r0 - 2 + ri, 0), H - 1);
-            const char* sbase = reinterpret_cast<const char*>(p.in) + ((size_t)(n * H + grow) * W * C) * 4 + (size_t)within * 16;
-            const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem + buf * RAW_BYTES + j * 1024;
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane * 16), "s"(dst), "s"(sbase) : "memory");
-        }
-    };
-    const int first = t_begin + jw;
-    const int n_my = first < t_end ? (t_end - first + p.wgs_per_xcd - 1) / p.wgs_per_xcd : 0;
-    if (n_my == 0) return;                                          // (whole workgroup)
-    auto tile_of = [&](int k) { return first + k * p.wgs_per_xcd; };
-    auto convert_tile = [&](int k, int rb, int xb) {                // raw[rb] -> input planes X[xb] of tile k
-        const int tile = tile_of(k);
-        const int n = tile / p.tiles_per_sample, r0 = (tile - n * p.tiles_per_sample) * R;
-        (void)n;
-        float ta = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < NQ / NTH; ++kk) {
-            const int q = kk * NTH + tid;
-            const int px = q / C4, c4 = q % C4;
-            const int ri = px / W, col = px - ri * W;
-            const int grow = r0 - 2 + ri;
-            float4 v = *reinterpret_cast<const float4*>(smem + rb * RAW_BYTES + q * 16);
-            if (grow < 0 || grow >= H) v = make_float4(0.f, 0.f, 0.f, 0.f);
-            v = elu4(v);
-            unsigned char* dst = smem + X_OFF + xb * XSZ + (c4 >> 1) * XPS + (ri * WP + col + 1) * 16 + (c4 & 1) * 8;
-            if constexpr (MODE == 2) {
-                StageScale ss{scale1, ta};
-                scale_track(v, &ss);
-                ta = ss.amax;
-                uint2 h, l;
-                split_f16x2(v, scale1, h, l);
-                *reinterpret_cast<uint2*>(dst) = h;
-                *reinterpret_cast<uint2*>(dst + KGS * XPS) = l;
-            } else {
-                f16x4 h;
-                h[0] = (_Float16)v.x; h[1] = (_Float16)v.y; h[2] = (_Float16)v.z; h[3] = (_Float16)v.w;
-                *reinterpret_cast<f16x4*>(dst) = h;
-            }
-        }
-        if constexpr (MODE == 2) pair_range_tile(ta, scale1, rbits, p.calib);
-    };
-    // the conversion waves request tile 0; the barrier that opens iteration 0 publishes it (and the padding zeros)
-    if (role == 2) {
-        issue_dma(tile_of(0), 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // filter fragments
-    }
-    // one convolution over units `sub`, `sub + 2`, ...: acc[i] = D[16 couts of this wave][16 pixels of unit i]
-    auto conv = [&](auto cvc, const int plane_off, const int PS, auto nuc, auto nutc, f32x4v* acc) {
-        constexpr int NU = decltype(nuc)::value, NUT = decltype(nutc)::value;   // (cvc: which convolution -- each role holds only its own fragments)
-        constexpr int DU = UROWS * WP * 16;                            // bytes from a wave's unit i to its unit i + 1
-        // source pixel of tap (0, 0) of the wave's first unit = plane row urow0 (the row above the output row), slot column ucol (-1 + 1)
-        const int ub0 = plane_off + kq * PS + (urow0 * WP + ucol) * 16;
-        // flat walk over (tap, unit) steps; the X fragments of a step are requested D - 1 steps ahead of its MFMAs through a
-        // ring of statically indexed registers (the scheduler would otherwise hoist every read of the loop and spill)
-        constexpr int NS = 9 * KH * NU, D = NT == 2 ? 3 : 6;             // steps: (tap, k-half, unit)
-        f16x8 ring[D][NT];
-        auto ld = [&](int s) {                                          // s is a compile-time constant at every call
-            const int tap = s / (KH * NU), kh = (s / NU) % KH, i = s % NU;
-            const int off = i * DU + ((tap / 3) * WP + (tap % 3)) * 16 + kh * 4 * PS;
-            if (NUT % USTEP == 0 || u0 + USTEP * i < NUT) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    ring[s % D][t] = *reinterpret_cast<const f16x8*>(smem + ub0 + (off + t * KGS * PS));
-            }
-        };
-#pragma unroll
-        for (int s = 0; s < D - 1; ++s) ld(s);
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int tap = s / (KH * NU), kh = (s / NU) % KH, i = s % NU;
-            if (s + D - 1 < NS) ld(s + D - 1);
-            if (NUT % USTEP == 0 || u0 + USTEP * i < NUT) {
-                const f16x8 xh = ring[s % D][0];
-                const f16x8 wh = __builtin_bit_cast(f16x8, wf[tap][kh][0]);
-                // the first matrix instruction of a unit takes a literal zero as its addend (no register zeroing per tile)
-                const f32x4v c0 = (tap == 0 && kh == 0) ? f32x4v{0.f, 0.f, 0.f, 0.f} : acc[i];
-                if constexpr (NT == 2) {
-                    const f16x8 xl = ring[s % D][NT - 1];
-                    const f16x8 wl = __builtin_bit_cast(f16x8, wf[tap][kh][NT - 1]);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl, c0, 0, 0, 0);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh, acc[i], 0, 0, 0);
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, acc[i], 0, 0, 0);
-                } else {
-                    acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh, c0, 0, 0, 0);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-
-
-    for (int it = 0; it < n_my + 2; ++it) {
-        lds_barrier();
-        if (role == 2) {
-            // (two tiles in flight -- the conversion waves counting themselves in through LDS before they reuse a raw buffer --
-            // measured slower: the waiting waves take issue slots from the matrix waves)
-            if (it + 1 < n_my) issue_dma(tile_of(it + 1), (it + 1) & 1);  // raw[(it+1)&1]: tile it-1's copy, converted an iteration ago
-            if (it < n_my) convert_tile(it, it & 1, it & 1);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // tile it+1 has landed before the next barrier publishes it
-            continue;
-        }
-        if (role == 0) {
-            const int t1 = it - 1;
-            if (t1 < 0 || t1 >= n_my) continue;
-            const int tile = tile_of(t1);
-            const int n = tile / p.tiles_per_sample, r0 = (tile - n * p.tiles_per_sample) * R;
-            (void)n;
-            // (3) conv1 on the RM intermediate rows -> ELU -> split -> intermediate planes
-            {
-                f32x4v acc[NU1];
-                conv(std::integral_constant<int, 0>{}, X_OFF + (t1 & 1) * XSZ, XPS, std::integral_constant<int, NU1>{}, std::integral_constant<int, NU1T>{}, acc);
-                const int cq = 4 * hf + kq;                                    // channel quad of this lane's four outputs
-                float tb = 0.f;
-#pragma unroll
-                for (int i = 0; i < NU1; ++i) {
-                    if (u0 + USTEP * i < NU1T) {
-                        const int prow = urow0 + i * UROWS, pcol = ucol;
-                        const int grow = r0 - 1 + prow;
-                        float4 v = make_float4(acc[i][0] * descale1, acc[i][1] * descale1, acc[i][2] * descale1, acc[i][3] * descale1);
-                        v = elu4(v);
-                        if (grow < 0 || grow >= H) v = make_float4(0.f, 0.f, 0.f, 0.f);    // zero padding of conv2, not conv1 of padding
-                        unsigned char* dst = smem + M_OFF + (t1 & 1) * MSZ + (cq >> 1) * MPS + (prow * WP + pcol + 1) * 16 + (cq & 1) * 8;
-                        if constexpr (MODE == 2) {
-                            StageScale ss{scale2, tb};
-                            scale_track(v, &ss);
-                            tb = ss.amax;
-                            uint2 h, l;
-                            split_f16x2(v, scale2, h, l);
-                            *reinterpret_cast<uint2*>(dst) = h;
-                            *reinterpret_cast<uint2*>(dst + KGS * MPS) = l;
-                        } else {
-                            f16x4 h;
-                            h[0] = (_Float16)v.x; h[1] = (_Float16)v.y; h[2] = (_Float16)v.z; h[3] = (_Float16)v.w;
-                            *reinterpret_cast<f16x4*>(dst) = h;
-                        }
-                    }
-                }
-                if constexpr (MODE == 2) pair_range_tile(tb, scale2, rbits, p.calib ? p.calib + 1 : nullptr);
-            }
-
-            continue;
-        }
-        const int t2 = it - 2;
-        if (t2 < 0 || t2 >= n_my) continue;
-        const int tile = tile_of(t2);
-        const int n = tile / p.tiles_per_sample, r0 = (tile - n * p.tiles_per_sample) * R;
-
-        // (4) conv2 on the R output rows, + residual, store
-        {
-            f32x4v acc[NU2];
-            // the residual operand: requested before the K loop (an L2 hit: this workgroup's DMA fetched the same lines), used after it
-            const int cq = 4 * hf + kq;
-            float4 xr[NU2];
-            constexpr int DO = UROWS * W * C;                               // elements from a wave's unit i to its unit i + 1
-            const unsigned o0 = (unsigned)(((n * H + r0 + urow0) * W + ucol) * C + cq * 4);
-#pragma unroll
-            for (int i = 0; i < NU2; ++i)
-                if (NU2T % USTEP == 0 || u0 + USTEP * i < NU2T) xr[i] = *reinterpret_cast<const float4*>(p.in + o0 + i * DO);
-            conv(std::integral_constant<int, 1>{}, M_OFF + (t2 & 1) * MSZ, MPS, std::integral_constant<int, NU2>{}, std::integral_constant<int, NU2T>{}, acc);
-            // everything this wave has in flight -- the residual, its pieces of the next tile's DMA -- has landed; the stores below
-            // are never waited for explicitly (the same wait one iteration later covers them)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int i = 0; i < NU2; ++i) {
-                if (NU2T % USTEP == 0 || u0 + USTEP * i < NU2T) {
-                    float4 y;
-                    y.x = fmaf(acc[i][0], descale2, xr[i].x); y.y = fmaf(acc[i][1], descale2, xr[i].y);
-                    y.z = fmaf(acc[i][2], descale2, xr[i].z); y.w = fmaf(acc[i][3], descale2, xr[i].w);
-                    st_out(p.out + o0 + i * DO, y);
-                }
-            }
-        }
-    }
-    if constexpr (MODE == 2) {
-        if (rbits && (threadIdx.x & 63) == 0) atomicOr(p.range_flag, rbits);
-    }
-}
-
-
-
-// The pipeline of conv_pair_p3_kernel WITHOUT THE HALO WORK (W = 16, 32 channels): a workgroup owns a contiguous run of tiles, so
-// the rows two vertically adjacent tiles share are converted and convolved once.  The operand planes are rings over rows:
+// The same block as a three-stage pipeline over a RUN of tiles (W = 16, 32 channels; the row-ring kernel): one persistent workgroup
+// per CU of twelve waves in three roles of four --
+//   role 2 (conversion): keeps one item of LDS-DMA in flight and turns the raw copy of item i into rows of the operand planes X;
+//   role 0 (conv1):      K loop of conv1 on the X rows of item i - 1, ELU, split -> rows of the intermediate planes M;
+//   role 1 (conv2):      K loop of conv2 on the M rows of item i - 2, + x, store.
+// The raw copy is double buffered and the planes hold three items (below), so ONE workgroup barrier per item is all the
+// synchronisation there is; each role keeps only its own filter fragments (72 registers in f16x2), which is what lets three waves
+// share a SIMD (168 registers each): two of them are always inside a K loop while the third does the vector-ALU work.
+// A workgroup owns a contiguous run of tiles, so the rows two vertically adjacent tiles share are converted and convolved once.
+// The operand planes are rings over rows:
 //   X (conv1's input, fp16 terms): 24 rows in three slots of 8 + a 4-row copy of rows 20..23 in front of row 0;
 //   M (the intermediate):          24 rows in three slots of 8 + a 2-row copy of rows 22, 23 in front of row 0.
 // Item k of the run uses slot k % 3.  A TILE item (output rows r0 .. r0+7 of sample n) converts the EIGHT input rows r0+2 .. r0+9
@@ -596,13 +295,20 @@ __global__ __launch_bounds__(192 * NW, 3) void conv_pair_p3_kernel(PairParams p)
 // rows before the slot are the previous item's last four) and the eight output rows (conv2 reads M rows slot-2 .. slot+7).  Where no
 // previous tile of the same sample precedes it in the run -- the run's first tile, the first tile of every sample -- a PRE item
 // comes first: it fills only the last four X rows (input rows r0-2 .. r0+1; zeros outside the image) and the last two M rows (r0-1,
-// r0) of its slot and stores nothing.  Against conv_pair_p3_kernel a sample of 64 rows converts 68 rows instead of 96, evaluates
-// conv1 on 66 rows instead of 80 and reads every input row from memory once (+ the PRE rows of a run that starts mid-sample).
+// r0) of its slot and stores nothing.  A sample of 64 rows converts 68 rows and evaluates conv1 on 66 (a pipeline whose every tile
+// brings its own halo: 96 and 80) and reads every input row from memory once (+ the PRE rows of a run that starts mid-sample).
 // The copies in front of row 0 make every window contiguous: a value written to rows 20..23 (X) / 22, 23 (M) is written twice.
-// Each role advances its own cursor over the run (scalar registers); one workgroup barrier per item as before -- the writer of
-// iteration `it` (X slot it % 3, M slot (it - 1) % 3) never touches the rows the readers of that iteration use (X: slot (it - 1) % 3
-// and the four rows before it; M: slot (it - 2) % 3 and the two rows before it).
-// Every output is the same sum in the same order as in the two kernels above: identical bit for bit.
+// Each role advances its own cursor over the run (scalar registers); the writer of iteration `it` (X slot it % 3, M slot
+// (it - 1) % 3) never touches the rows the readers of that iteration use (X: slot (it - 1) % 3 and the four rows before it; M: slot
+// (it - 2) % 3 and the two rows before it).
+// Every output is the same sum in the same order as in conv_pair_kernel: identical bit for bit.
+// Measurements behind the three roles, from the per-tile-halo form of this pipeline (removed; history: 54de329), 13 600 tiles: 180 us
+// in the network against 203 for conv_pair_kernel (matrix pipe 0.57 busy against 0.51).  Two roles -- four matrix waves that keep
+// both convolutions' fragments, four conversion waves -- were slower than conv_pair_kernel, 256 us against 244 back to back: ONE
+// matrix wave per SIMD does not keep the matrix pipe fed.  The same holds inside the pipeline: matrix waves that own all 32 output
+// channels of their units -- half the LDS reads, two waves per matrix role -- ran 279 us against 231.  Two items in flight (the
+// conversion waves counting themselves in through LDS before they reuse a raw buffer) measured slower as well: the waiting waves
+// take issue slots from the matrix waves.
 template <int MODE>
 __global__ __launch_bounds__(768, 3) void conv_pair_roll_kernel(PairParams p) {
     constexpr int W = 16, R = 8, C = 32, NW = 4, NTH = 64 * NW;
@@ -863,19 +569,21 @@ __global__ __launch_bounds__(768, 3) void conv_pair_roll_kernel(PairParams p) {
 // for 32-channel NHWC fp32 tensors, 16 pixels wide.  Unfused, a stage is a max-pool launch (one tensor read, one written) and a
 // convolution launch (read it again, write the result, read two residual operands): at 223 MB per tensor the CRP block of the
 // full-resolution level moves 2.2 GB per step; here the pooled tensor never exists in memory.
-// The pipeline of conv_pair_p3_kernel with ONE convolution: a persistent workgroup per CU of twelve waves --
+// A two-stage pipeline over tiles, double buffered: a persistent workgroup per CU of twelve waves in two roles --
 //   conversion (4 waves, one per SIMD): keep the R + 6 raw rows of the next tile in flight by LDS-DMA; pool tile i -- the vertical
 //           5-maximum in registers from the LDS copy, the horizontal one by DPP row shifts (a 16-pixel row is one DPP row;
 //           out-of-image columns leave the lane's running maximum alone, rows outside the image were requested from the nearest row
 //           inside: both are what MaxPool2d's -inf padding computes) --, ELU, two fp16 terms -> operand planes X[i & 1];
 //   matrix (8 waves, two per SIMD): the K loop of the convolution on X[(i-1) & 1], two units (image rows) per wave, filter
 //           fragments resident in registers; + residual operands (requested before the K loop), store.
-// One workgroup barrier per tile.  The tile is bound by VECTOR-INSTRUCTION ISSUE, not by the matrix pipe: pooling costs ~20 vector
-// instructions per value (8 vertical v_max3 + 20 DPP maxima + ELU 16 + split 8 + ... per four values), and every arrangement of
-// the roles measured the same ~5-7 k cycles per tile (-DSBC_PAIR_TIMING: 4 conversion + 8 matrix waves 6.9 k with the builtins'
-// ten-instruction DPP maxima; 8 + 4: 6.2 k, one matrix wave per SIMD needs 46 cycles per matrix instruction; 8 + 8: 5.3 k).  Four
-// conversion waves issue the fewest instructions per tile (five pooled rows per lane share nine LDS reads).  Conversion wave w owns channel quads 2 (w & 3), + 1 and one half of the pooled rows: both pool passes of a value stay
-// inside one wave, so the role needs no synchronisation of its own.
+// Both plane sets and the raw copies exist twice (the raw copy three times, see NRAW), so the writer of iteration i never touches
+// what the readers of that iteration use: ONE workgroup barrier per tile.  The tile is bound by VECTOR-INSTRUCTION ISSUE, not by the
+// matrix pipe: pooling costs ~20 vector instructions per value (8 vertical v_max3 + 20 DPP maxima + ELU 16 + split 8 + ... per four
+// values), and every arrangement of the roles measured the same ~5-7 k cycles per tile (per-phase cycle counters of an instrumented
+// build, history: 54de329: 4 conversion + 8 matrix waves 6.9 k with the builtins' ten-instruction DPP maxima; 8 + 4: 6.2 k, one
+// matrix wave per SIMD needs 46 cycles per matrix instruction; 8 + 8: 5.3 k).  Four conversion waves issue the fewest instructions
+// per tile (five pooled rows per lane share nine LDS reads).  Conversion wave w owns channel quads 2 (w & 3), + 1 and one half of the
+// pooled rows: both pool passes of a value stay inside one wave, so the role needs no synchronisation of its own.
 __device__ __forceinline__ float4 vmax5(float4 a, float4 b, float4 c, float4 d, float4 e) {
     // (v_max3_f32 by hand: fmaxf() costs a canonicalising v_max per operand)
     float4 m;
@@ -973,9 +681,6 @@ __global__ __launch_bounds__(64 * (8 + NWC)) void conv_pool_kernel(PairParams p)
 #pragma unroll
         for (int j = 0; j < NRG; ++j) {
             if (j == NRG - 1 && !full) break;
-#ifdef SBC_POOL_SKIP   // timing probe (wrong results): no pooling -- what a direct pipelined kernel for a plain 3x3 layer would cost
-            float4 v = rv[j + 2];
-#else
             float4 v = vmax5(rv[j], rv[j + 1], rv[j + 2], rv[j + 3], rv[j + 4]);
             // horizontal 5-maximum over the 16 lanes of the row (= the image row): v_max_f32 with a DPP row shift on its first source;
             // a lane whose shifted source lies outside the row is disabled for that instruction and keeps its running maximum.  By hand:
@@ -996,7 +701,6 @@ __global__ __launch_bounds__(64 * (8 + NWC)) void conv_pool_kernel(PairParams p)
                     : "=&v"(m.x), "=&v"(m.y), "=&v"(m.z), "=&v"(m.w) : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
                 v = m;
             }
-#endif
             if (p.flags & SBC_PRO_ELU) v = elu4(v);
             const int prow = prow0 + j;
             const int grow = r0 - 1 + prow;
@@ -1018,22 +722,15 @@ __global__ __launch_bounds__(64 * (8 + NWC)) void conv_pool_kernel(PairParams p)
         }
         if constexpr (MODE == 2) pair_range_tile(ta, scale1, rbits, p.calib);
     };
-#ifdef SBC_PAIR_TIMING
-    unsigned long long pt[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pt_last = __builtin_readcyclecounter();
-#endif
     // The two roles run SEPARATE loops with the same barrier sequence (n_my + 1 workgroup barriers each): in one loop the filter
     // fragments (72 registers) would stay allocated through the conversion code, which then spills at 128 registers per wave.
     if (!matrix) {
         issue_dma(tile_of(0), 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         for (int it = 0; it < n_my + 1; ++it) {
-            PT_MARK(3);                                  // (the role's work of the last iteration)
             lds_barrier();
-            PT_MARK(0);
             if (it + 1 < n_my) issue_dma(tile_of(it + 1), (it + 1) % NRAW);
-            PT_MARK(1);
             if (it < n_my) convert_tile(it, it % NRAW, it & 1);
-            PT_MARK(2);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
     } else {
@@ -1049,9 +746,7 @@ __global__ __launch_bounds__(64 * (8 + NWC)) void conv_pool_kernel(PairParams p)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const bool res2_lds = p.res2 == p.in;            // CRP: the second residual operand is this launch's own input
         for (int it = 0; it < n_my + 1; ++it) {
-            PT_MARK(7);
             lds_barrier();
-            PT_MARK(4);
             const int t1 = it - 1;
             if (t1 < 0) continue;
             const int tile = tile_of(t1);
@@ -1098,9 +793,7 @@ __global__ __launch_bounds__(64 * (8 + NWC)) void conv_pool_kernel(PairParams p)
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            PT_MARK(5);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            PT_MARK(6);
 #pragma unroll
             for (int i = 0; i < NU; ++i) {
                 float4 y = make_float4(acc[i][0] * descale1, acc[i][1] * descale1, acc[i][2] * descale1, acc[i][3] * descale1);
@@ -1126,105 +819,57 @@ __global__ __launch_bounds__(64 * (8 + NWC)) void conv_pool_kernel(PairParams p)
     if constexpr (MODE == 2) {
         if (rbits && (threadIdx.x & 63) == 0) atomicOr(p.range_flag, rbits);
     }
-#ifdef SBC_PAIR_TIMING
-    // wave 0 of the matrix role and of the conversion role: [barrier, dma issue, convert, load wait | barrier, K loop, residual wait, store]
-    if (lane == 0 && (wv == 0 || wv == NWM) && p.dbg)
-        for (int k = 0; k < 8; ++k) atomicAdd(p.dbg + k, pt[k]);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------ dispatch
+// Common tail of the launchers below: tiles of R rows of one sample; each XCD owns a contiguous eighth of them and runs `per_cu`
+// persistent workgroups for each of its share of the CUs the plan may count on -- never more than it has tiles.
+template <class K>
+static int launch_tiles(K kern, const PairParams& p0, int R, int per_cu, int threads, size_t lds, hipStream_t stream, bool dry) {
+    { const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
+    if (dry) return SBC_OK;
+    PairParams p = p0;
+    p.tiles_per_sample = p.H / R;
+    p.ntiles = p.B * p.tiles_per_sample;
+    int dev = 0, cus = 256;
+    SBC_CHECK_HIP(hipGetDevice(&dev));
+    SBC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    p.tiles_per_xcd = (p.ntiles + 7) / 8;
+    p.wgs_per_xcd = max(1, min(per_cu * persistent_cus(cus) / 8, p.tiles_per_xcd));
+    hipLaunchKernelGGL(kern, dim3(8 * p.wgs_per_xcd), dim3(threads), lds, stream, p);
+    SBC_CHECK_HIP(hipGetLastError());
+    return SBC_OK;
+}
+
 template <int W, int R, int MODE, int NW = 4, int C = 32>
-static int launch_pair(const PairParams& p0, hipStream_t stream, bool dry) {
+static int launch_pair(const PairParams& p, hipStream_t stream, bool dry) {
     constexpr int NT = MODE == 2 ? 2 : 1;
     constexpr int RI = R + 4, RM = R + 2, WP = W + 2;
     constexpr int XPS = (RI * WP * 16 + 255) / 256 * 256, MPS = (RM * WP * 16 + 255) / 256 * 256;
     constexpr size_t lds = (size_t)RI * W * C * 4 + (size_t)NT * (C / 8) * (XPS + MPS);
     constexpr int PER_CU = NW == 4 ? 2 : 1;                              // workgroups per CU (two waves per SIMD either way)
     static_assert(lds <= 160 * 1024 / PER_CU, "LDS of the resident workgroups");
-    auto kern = conv_pair_kernel<W, R, MODE, NW, C>;
-    { const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
-    if (dry) return SBC_OK;
-    PairParams p = p0;
-    p.tiles_per_sample = p.H / R;
-    p.ntiles = p.B * p.tiles_per_sample;
-    int dev = 0, cus = 256;
-    SBC_CHECK_HIP(hipGetDevice(&dev));
-    SBC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
-    p.wgs_per_xcd = max(1, min(PER_CU * persistent_cus(cus) / 8, p.tiles_per_xcd));
-    hipLaunchKernelGGL(kern, dim3(8 * p.wgs_per_xcd), dim3(64 * NW), lds, stream, p);
-    SBC_CHECK_HIP(hipGetLastError());
-    return SBC_OK;
-}
-
-template <int W, int R, int MODE, int NW = 4, int C = 32>
-static int launch_pair_p3(const PairParams& p0, hipStream_t stream, bool dry) {
-    constexpr int NT = MODE == 2 ? 2 : 1;
-    constexpr int RI = R + 4, RM = R + 2, WP = W + 2;
-    constexpr int XPS = (RI * WP * 16 + 255) / 256 * 256, MPS = (RM * WP * 16 + 255) / 256 * 256;
-    constexpr size_t lds = (size_t)2 * RI * W * C * 4 + (size_t)NT * (C / 8) * 2 * (XPS + MPS);
-    static_assert(lds <= 160 * 1024, "LDS of the one resident workgroup");
-    auto kern = conv_pair_p3_kernel<W, R, MODE, NW, C>;
-    { const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
-    if (dry) return SBC_OK;
-    PairParams p = p0;
-    p.tiles_per_sample = p.H / R;
-    p.ntiles = p.B * p.tiles_per_sample;
-    int dev = 0, cus = 256;
-    SBC_CHECK_HIP(hipGetDevice(&dev));
-    SBC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
-    p.wgs_per_xcd = max(1, min(persistent_cus(cus) / 8, p.tiles_per_xcd));
-    hipLaunchKernelGGL(kern, dim3(8 * p.wgs_per_xcd), dim3(192 * NW), lds, stream, p);
-    SBC_CHECK_HIP(hipGetLastError());
-    return SBC_OK;
+    return launch_tiles(conv_pair_kernel<W, R, MODE, NW, C>, p, R, PER_CU, 64 * NW, lds, stream, dry);
 }
 
 template <int MODE>
-static int launch_pair_roll(const PairParams& p0, hipStream_t stream, bool dry) {
+static int launch_pair_roll(const PairParams& p, hipStream_t stream, bool dry) {
     constexpr int NT = MODE == 2 ? 2 : 1, ROWB = 18 * 16;
     constexpr int XPS = (28 * ROWB + 255) / 256 * 256, MPS = (26 * ROWB + 255) / 256 * 256;
     constexpr size_t lds = (size_t)2 * 8 * 16 * 32 * 4 + (size_t)NT * 4 * (XPS + MPS);
     static_assert(lds <= 160 * 1024, "LDS of the one resident workgroup");
-    auto kern = conv_pair_roll_kernel<MODE>;
-    { const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
-    if (dry) return SBC_OK;
-    PairParams p = p0;
-    p.tiles_per_sample = p.H / 8;
-    p.ntiles = p.B * p.tiles_per_sample;
-    int dev = 0, cus = 256;
-    SBC_CHECK_HIP(hipGetDevice(&dev));
-    SBC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
-    p.wgs_per_xcd = max(1, min(persistent_cus(cus) / 8, p.tiles_per_xcd));
-    hipLaunchKernelGGL(kern, dim3(8 * p.wgs_per_xcd), dim3(768), lds, stream, p);
-    SBC_CHECK_HIP(hipGetLastError());
-    return SBC_OK;
+    return launch_tiles(conv_pair_roll_kernel<MODE>, p, 8, 1, 768, lds, stream, dry);
 }
 
 template <int MODE>
-static int launch_pool(const PairParams& p0, hipStream_t stream, bool dry) {
+static int launch_pool(const PairParams& p, hipStream_t stream, bool dry) {
     constexpr int W = 16, R = 8, C = 32, NT = MODE == 2 ? 2 : 1;
     constexpr int RI = R + 6, RP = R + 2, WP = W + 2;
     constexpr int XPS = (RP * WP * 16 + 255) / 256 * 256;
     constexpr size_t lds = (size_t)3 * RI * W * C * 4 + (size_t)2 * NT * (C / 8) * XPS;
     static_assert(lds <= 160 * 1024, "LDS of the one resident workgroup");
     constexpr int NWC = 4;
-    auto kern = conv_pool_kernel<W, R, MODE, NWC, C>;
-    { const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
-    if (dry) return SBC_OK;
-    PairParams p = p0;
-    p.tiles_per_sample = p.H / R;
-    p.ntiles = p.B * p.tiles_per_sample;
-    int dev = 0, cus = 256;
-    SBC_CHECK_HIP(hipGetDevice(&dev));
-    SBC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    p.tiles_per_xcd = (p.ntiles + 7) / 8;
-    p.wgs_per_xcd = max(1, min(persistent_cus(cus) / 8, p.tiles_per_xcd));
-    hipLaunchKernelGGL(kern, dim3(8 * p.wgs_per_xcd), dim3(64 * (8 + NWC)), lds, stream, p);
-    SBC_CHECK_HIP(hipGetLastError());
-    return SBC_OK;
+    return launch_tiles(conv_pool_kernel<W, R, MODE, NWC, C>, p, R, 1, 64 * (8 + NWC), lds, stream, dry);
 }
 
 int launch_conv_pool(const sbc_op& op, hipStream_t stream, bool dry) {
@@ -1246,7 +891,6 @@ int launch_conv_pool(const sbc_op& op, hipStream_t stream, bool dry) {
     p.res1 = (const float*)op.res1; p.res2 = (const float*)op.res2; p.flags = op.flags;
     p.B = op.B; p.H = op.H;
     p.calib = (float*)op.calib;
-    p.dbg = (unsigned long long*)op.aux;
     if (x2) {
         unsigned* word = nullptr;
         const int rc = range_flag_ptr(&word);
@@ -1269,7 +913,6 @@ int launch_conv_pair(const sbc_op& op, hipStream_t stream, bool dry) {
     p.in = (const float*)op.in; p.out = (float*)op.out;
     p.w1 = (const uint4*)op.weight_split; p.w2 = (const uint4*)op.weight2_split;
     p.B = op.B; p.H = op.H;
-    p.dbg = (unsigned long long*)op.aux;
     p.calib = (float*)op.calib;
     if (x2) {
         unsigned* word = nullptr;
@@ -1286,20 +929,12 @@ int launch_conv_pair(const sbc_op& op, hipStream_t stream, bool dry) {
         set_error("conv_pair: no 64-channel kernel for image %dx%d", op.H, op.W);
         return SBC_ERR_UNSUPPORTED;
     }
-#ifdef SBC_WITH_PAIR32   // tools/experiments/conv_pair32.hip (round 6: the 32-cycle matrix shape with the vector work inside the K loops; measured slower)
-    if (x2 && op.W == 16 && op.H % 8 == 0) return launch_pair32(p, stream, dry);
-#endif
-    // many tiles per CU: the three-stage pipeline (identical results; below ~16 tiles per workgroup its fill and drain cost more
-    // than it gains: 1040 tiles 21.8 us against 21.3, 6800 tiles 112 against 122, 13600 tiles 230 against 242)
-    static const bool no_p3 = getenv("SBC_NO_PAIR_P3") != nullptr;           // A/B aid
-    static const bool no_roll = getenv("SBC_NO_PAIR_ROLL") != nullptr;       // A/B aid: the pipeline with per-tile halos
-    // (from 1024 tiles: a workgroup's run is then at least four tiles at full grid width, eight at half width -- 850 trajectories per
-    // GPU 2.51 -> 2.44 ms per step, 425: 1.57 -> 1.53 against the tile-at-a-time kernel; round 4's pipeline wanted 4096)
-    static const long roll_min = getenv("SBC_PAIR_ROLL_MIN_TILES") ? atol(getenv("SBC_PAIR_ROLL_MIN_TILES")) : 1024;   // (the variable: A/B aid)
-    if (!no_p3 && !no_roll && op.W == 16 && op.H % 8 == 0 && (long)op.B * (op.H / 8) >= roll_min)
+    // 16-pixel rows, H % 8 == 0: the row-ring kernel from 1024 tiles -- a workgroup's run is then at least four tiles at full grid
+    // width, eight at half width (850 trajectories per GPU 2.51 -> 2.44 ms per step, 425: 1.57 -> 1.53 against the tile kernel; below
+    // ~16 tiles per workgroup a pipeline's fill and drain cost more than it gains: 1040 tiles 21.8 us against 21.3 for the
+    // per-tile-halo pipeline, 6800 tiles 112 against 122, 13600 tiles 230 against 242) -- the tile kernel below (identical results)
+    if (op.W == 16 && op.H % 8 == 0 && (long)op.B * (op.H / 8) >= 1024)
         return x2 ? launch_pair_roll<2>(p, stream, dry) : launch_pair_roll<1>(p, stream, dry);
-    if (!no_p3 && op.W == 16 && op.H % 8 == 0 && (long)op.B * (op.H / 8) >= 4096)
-        return x2 ? launch_pair_p3<16, 8, 2>(p, stream, dry) : launch_pair_p3<16, 8, 1>(p, stream, dry);
     if (op.W == 16 && op.H % 8 == 0) return x2 ? launch_pair<16, 8, 2>(p, stream, dry) : launch_pair<16, 8, 1>(p, stream, dry);
     // 32-pixel rows (the half-resolution level of a 256 x 64 array): tiles of 4 rows, wave pair `sub` owns column block `sub`
     if (op.W == 32 && op.H % 4 == 0 && f16w) return launch_pair<32, 4, 1, 4>(p, stream, dry);

@@ -23,16 +23,12 @@
 //      (the memory counter is in order); with SBC_EPI_MOMENTS_OUT also the (mean, M2) of the output's 128-pixel tiles for the
 //      InstanceNorm++ that reads it next (tile.h) -- whole tiles per wave, no exchange.
 // Five workgroup barriers per sample.  Everything is summed in an order that depends on the layer's shape only.
-// Timeline of a sample (-DSBC_RES_TIMELINE, tools/prof_res.py; profiles/r06_timeline_conv_res.txt): of 66 k clocks the two K loops take
+// Timeline of a sample (cycle-counter stamps of an instrumented build; profiles/r06_timeline_conv_res.txt): of 66 k clocks the two K loops take
 // 15 k and 22 k (the four waves that arrived first on their SIMDs finish each loop in 9 k, the other four get the matrix pipe afterwards --
 // and run conv2 beside the first four's epilogue), phases A and D 7 k each, the statistics 4 k, the epilogue of the late waves 9 k: a
 // CU moves its 256 KB per sample at ~50 GB/s whoever issues the requests.
-#include <stdlib.h>
 #include <type_traits>
 #include "conv_common.h"
-#ifndef RES_WD
-#define RES_WD 4
-#endif
 
 namespace sbc {
 
@@ -51,15 +47,11 @@ struct ResParams {
     unsigned* __restrict__ range_flag;
     float* __restrict__ calib;           // sbc_f16x2_calibrate: two amax slots (conv1's input, conv2's input), else NULL
     int B;
-    unsigned long long* dbg;             // SBC_RES_TIMELINE builds: clock stamps of block 0 (tools/prof_res.py)
+    // Keeps the argument block at 104 bytes.  conv_res_kernel reads gridDim.x from the implicit arguments that follow the block, at an offset
+    // that is an immediate in its code; with these eight bytes (a debug pointer until 54de329) the kernel's code is that commit's, instruction
+    // for instruction (tools/device_code_diff.py).  Drop them with the next change that alters this kernel's code anyway.
+    unsigned long long tail_pad;
 };
-
-#ifdef SBC_RES_TIMELINE
-// block 0 only: every wave's clock at 12 points of every sample -> dbg[(iteration * 8 + wave) * 16 + k]
-#define RS_T(k) do { if (blockIdx.x == 0 && p.dbg) { const unsigned long long _t = __builtin_readcyclecounter(); if (lane == 0) p.dbg[((n / gridDim.x) * 8 + wave) * 16 + (k)] = _t; } } while (0)
-#else
-#define RS_T(k) do { } while (0)
-#endif
 
 // sum over the 16 lanes of a DPP row (= the 16 pixels of a unit for one k-quarter); every lane of the row gets the total
 __device__ __forceinline__ float row_sum16(float v) {
@@ -89,7 +81,7 @@ __global__ __launch_bounds__(512, 2) void conv_res_kernel(ResParams p) {
     // ---- filter fragments STREAM from L2 through a ring of WD taps (8 registers a tap), re-read for every sample.  (Round 5 kept one
     // convolution's 72 registers resident; with x resident as well -- below -- that does not fit.)  The first WD - 1 taps are requested
     // before the barrier in front of the convolution, tap + WD - 1 when tap starts: 2 x 768 matrix cycles ahead of its first use.
-    constexpr int WD = RES_WD;
+    constexpr int WD = 4;
     static_assert(WD % 2 == 0, "an odd ring depth makes hipcc merge the two K loops into one loop over a scratch-resident ring");
     uint4 wr[WD][NT];
     const uint4* wb = nullptr;                          // this lane's fragment of tap 0, term 0 of the convolution in flight
@@ -140,9 +132,7 @@ __global__ __launch_bounds__(512, 2) void conv_res_kernel(ResParams p) {
 
     for (; n < p.B; n += gridDim.x) {
         // every wave is through the previous sample's conv2 (first sample: the planes are zeroed)
-        RS_T(0);
         __syncthreads();
-        RS_T(1);
         // this lane's slot in the operand planes (the same in phases A and D): pixel c of plane row 16 sub + 1, k-group cq >> 1, half cq & 1
         int lq = lane;
         asm volatile("" : "+v"(lq));                       // (formed per sample, see load_w)
@@ -163,9 +153,7 @@ __global__ __launch_bounds__(512, 2) void conv_res_kernel(ResParams p) {
             *reinterpret_cast<uint2*>(dst0 + i * WP * 16 + KGS * PS) = l;
         }
         pair_range_tile(ta, scale1, rbits, p.calib);
-        RS_T(2);
         lds_barrier();
-        RS_T(3);
 
         // one convolution over this wave's 16 rows: acc[i] = D[16 couts][16 pixels of row 16 sub + i]
         f32x4v acc[NU];
@@ -221,7 +209,6 @@ __global__ __launch_bounds__(512, 2) void conv_res_kernel(ResParams p) {
         // ---- B: conv1
         conv();
         load_w(p.w2);
-        RS_T(4);
         // ---- C: t = conv1 + bias1 (in place), statistics of t over the whole sample
         {
 #pragma unroll
@@ -243,9 +230,7 @@ __global__ __launch_bounds__(512, 2) void conv_res_kernel(ResParams p) {
                     *reinterpret_cast<float2*>(red + ((2 * sub + T) * C + cq * 4 + r) * 2) = make_float2(mean[r], m2[r]);
             }
         }
-        RS_T(5);
         lds_barrier();
-        RS_T(6);
         if (tid < C) {
             // one channel each: the 8 tiles in order (ops.hip: inorm_from_moments_kernel), then -- the same 32 lanes of wave 0, through
             // LDS, every lane summing all 32 channels in index order -- the cross-channel "++" term, and norm2's (mu, scale, shift)
@@ -279,7 +264,6 @@ __global__ __launch_bounds__(512, 2) void conv_res_kernel(ResParams p) {
             nrm[2 * C + tid] = fmaf(ga, (m_c - m) * rs * al, be);
         }
         lds_barrier();
-        RS_T(7);
         const float4 nmu = *reinterpret_cast<const float4*>(nrm + cq * 4), nsc = *reinterpret_cast<const float4*>(nrm + C + cq * 4),
                      nsh = *reinterpret_cast<const float4*>(nrm + 2 * C + cq * 4);
         // ---- D: t -> norm2 -> ELU -> split -> the same planes (conv2's operand)
@@ -297,13 +281,10 @@ __global__ __launch_bounds__(512, 2) void conv_res_kernel(ResParams p) {
             *reinterpret_cast<uint2*>(dst0 + i * WP * 16 + KGS * PS) = l;
         }
         pair_range_tile(tb, scale2, rbits, p.calib ? p.calib + 1 : nullptr);
-        RS_T(8);
         lds_barrier();
-        RS_T(9);
         // ---- E: conv2
         conv();
         load_w(p.w1);                                       // (conv1's first taps for the next sample; harmless behind the last one)
-        RS_T(10);
         // ---- F: out = (conv2 x descale2 + bias2) + x -- the order of the unfused records: one rounding at the output's magnitude;
         // then the next sample's x is requested (AHEAD of the stores: the memory counter is in order, behind 16 stores phase A would
         // wait for every one of them to be acknowledged), the stores, the tile moments of the output
@@ -312,18 +293,15 @@ __global__ __launch_bounds__(512, 2) void conv_res_kernel(ResParams p) {
             acc[i][0] = fmaf(acc[i][0], descale2, b2.x) + xr[i].x; acc[i][1] = fmaf(acc[i][1], descale2, b2.y) + xr[i].y;
             acc[i][2] = fmaf(acc[i][2], descale2, b2.z) + xr[i].z; acc[i][3] = fmaf(acc[i][3], descale2, b2.w) + xr[i].w;
         }
-        RS_T(12);
         __builtin_amdgcn_sched_barrier(0);
         request_x(min(n + (int)gridDim.x, p.B - 1));       // (unconditional: behind a branch the new x lands in other registers and is
                                                             // COPIED at the end of the loop body -- after a wait for all of it)
-        RS_T(13);
         __builtin_amdgcn_sched_barrier(0);
         {
             float* const o = p.out + (size_t)(((n * H + sub * NU) * W + (lq & 15)) * C + (4 * hf + (lq >> 4)) * 4);
 #pragma unroll
             for (int i = 0; i < NU; ++i) st_out(o + i * W * C, make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]));
         }
-        RS_T(14);
         if (p.pm_out) {
 #pragma unroll
             for (int T = 0; T < 2; ++T) {
@@ -336,7 +314,6 @@ __global__ __launch_bounds__(512, 2) void conv_res_kernel(ResParams p) {
                 }
             }
         }
-        RS_T(11);
     }
     if (rbits && lane == 0) atomicOr(p.range_flag, rbits);
 }
@@ -366,9 +343,6 @@ int launch_res_block(const sbc_op& op, hipStream_t stream, bool dry) {
     p.stats1 = (const float*)op.stats; p.norm2 = (const float*)op.norm2;
     p.pm_out = (op.flags & SBC_EPI_MOMENTS_OUT) ? (float*)op.aux : nullptr;
     p.range_flag = word; p.calib = (float*)op.calib; p.B = op.B;
-#ifdef SBC_RES_TIMELINE
-    p.dbg = (op.flags & SBC_EPI_MOMENTS_OUT) ? nullptr : (unsigned long long*)op.aux;
-#endif
     int dev = 0, cus = 256;
     SBC_CHECK_HIP(hipGetDevice(&dev));
     SBC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));

@@ -11,22 +11,11 @@
 // cycles) -- and the vector ALU is free meanwhile for the ~240 transform + split instructions of the next step.
 // Because the split happens AFTER the input transform, the LDS tile stays fp32 ([pixel][CIN + 4], 144 B per pixel at
 // 32 channels) instead of the three bf16 planes of conv_x3.hip.
-#include <stdlib.h>
 #include "conv_common.h"
-#ifdef SBC_WITH_WSP   // tools/build_variant.sh wsp conv_wx3.hip -DSBC_WITH_WSP: the role-split experiment takes the layers it can
-namespace sbc { int launch_conv_wsp(const ConvParams& p, int cin, int cout, hipStream_t stream, bool dry); }
-#include "../../tools/experiments/conv_wsp.hip"
-#endif
 
 namespace sbc {
 
 constexpr int WX3_TS = 32;
-
-#ifdef SBC_WX3_TIMING   // tuning aid (tools/prof_conv.py WX3_TIMING=1): 100 MHz timestamps of wave 0 of every workgroup through p.up
-#define WT_MARK(k) do { if (tid == 0) wt[k] = wall_clock64(); } while (0)
-#else
-#define WT_MARK(k) do { } while (0)
-#endif
 
 // WPE: waves per SIMD the register allocation must allow (2 = 256 registers, 3 = 168).  A third resident workgroup per CU
 // is worth ~20 % where the kernel fits without spilling (32 -> 32 with 128-pixel tiles); the wider variants would spill.
@@ -81,10 +70,6 @@ __global__ __launch_bounds__(256 * NG, WPE) void conv_wx3_kernel(ConvParams p) {
 
     const TileGeom g = tile_geom(xcd_tile(blockIdx.x, gridDim.x), TM, p.B, dm, 1);
     float descale = 1.f, act_scale = 1.f;
-#ifdef SBC_WX3_TIMING
-    unsigned long long wt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    WT_MARK(0);
     {
         StageScale ss{1.f, 0.f};
         StageScale* const ssp = MODE == 2 ? &ss : nullptr;
@@ -97,7 +82,6 @@ __global__ __launch_bounds__(256 * NG, WPE) void conv_wx3_kernel(ConvParams p) {
         }
         float4 pf[NPF];
         stage_issue<CIN, NTHREADS, NPF>(pf, p.in, g, W, tid);
-        WT_MARK(1);
         // InstanceNorm++ statistics of the tile's samples through LDS (behind the staged tile and the T planes)
         float* st_lds = lds + p.stats_off;
         bool direct = false;
@@ -116,7 +100,6 @@ __global__ __launch_bounds__(256 * NG, WPE) void conv_wx3_kernel(ConvParams p) {
         if (!direct) stage_commit<CIN, NTHREADS, NPF, P2>(lds, pf, p.in, st_lds, sflags, g, dm, tid, 0, ssp);
         if constexpr (MODE == 2) f16x2_range_report(ss.amax, act_scale, p.range_flag, p.calib);
     }
-    WT_MARK(2);
     // T planes [xi][b][tile][TS]: overlay the staged tile when there is a single output block, else live behind it
     float* const tl = (NBLK == 1 ? lds : lds + (size_t)(g.multi ? TM + 1 : TM + 2 * W + 1) * S) + (size_t)grp * 8 * NTW * TS;
 
@@ -150,7 +133,6 @@ __global__ __launch_bounds__(256 * NG, WPE) void conv_wx3_kernel(ConvParams p) {
         }
     }
     __syncthreads();                                                  // staged tile visible
-    WT_MARK(3);
 
     for (int ph = grp; ph < PH; ph += NG) {
         f32x16 T[MB][NBP][2];
@@ -277,7 +259,6 @@ __global__ __launch_bounds__(256 * NG, WPE) void conv_wx3_kernel(ConvParams p) {
             }
         }
 
-        WT_MARK(4);
         if (NBLK == 1) __syncthreads();           // all waves are done with the staged tile (T planes overlay it)
 #pragma unroll
         for (int q = 0; q < NBP; ++q) {
@@ -293,7 +274,6 @@ __global__ __launch_bounds__(256 * NG, WPE) void conv_wx3_kernel(ConvParams p) {
                     for (int r = 0; r < 16; ++r) e[((r & 3) + 8 * (r >> 2)) * TS] = tv[r];
                 }
             __syncthreads();
-            WT_MARK(5);
             // finish: one (tile, channel quad) per thread and round
             float4 yk[4];                                                 // this thread's four outputs (SBC_EPI_MOMENTS_OUT)
 #pragma unroll
@@ -453,14 +433,6 @@ __global__ __launch_bounds__(256 * NG, WPE) void conv_wx3_kernel(ConvParams p) {
             if (q + 1 < NBP || ph + NG < PH) __syncthreads();
         }
     }
-#ifdef SBC_WX3_TIMING
-    WT_MARK(6);
-    if (tid == 0 && p.up && !(p.flags & SBC_EPI_UP)) {
-        unsigned long long* d = reinterpret_cast<unsigned long long*>(const_cast<float*>(p.up)) + (size_t)blockIdx.x * 8;
-        for (int k = 0; k < 7; ++k) d[k] = wt[k];
-        d[7] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | __builtin_amdgcn_s_getreg((31 << 11) | 4);
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------ dispatch
@@ -522,10 +494,6 @@ static int launch_wx3_sized(const ConvParams& p, hipStream_t stream, bool dry) {
     // 205 us with three 128-pixel workgroups per CU against 227 us with two 256-pixel ones); 256 only when 128 does
     // not tile the image
     constexpr bool mb2_ok = (COUT == 32);
-    static const bool force2 = getenv("SBC_WX3_MB2") != nullptr;                   // tuning aid
-    if constexpr (mb2_ok) {
-        if (force2 && fits(256)) return launch_wx3_mode<CIN, COUT, 2>(p, stream, dry);
-    }
     if (fits(128)) return launch_wx3_mode<CIN, COUT, 1>(p, stream, dry);
     if constexpr (mb2_ok) {
         if (fits(256)) return launch_wx3_mode<CIN, COUT, 2>(p, stream, dry);
@@ -536,9 +504,6 @@ static int launch_wx3_sized(const ConvParams& p, hipStream_t stream, bool dry) {
 int launch_conv_wx3(const ConvParams& p, int cin, int cout, hipStream_t stream, bool dry) {
     // power-of-two images with even sides only (every level the score network produces for Nt, Nr in {16, 64, 256})
     if (p.dil != 1 || p.hsh < 1 || p.wsh < 1) return 1;
-#ifdef SBC_WITH_WSP
-    { const int rc = launch_conv_wsp(p, cin, cout, stream, dry); if (rc <= 0) return rc; }
-#endif
     const int key = cin * 1000 + cout;
     switch (key) {
         case 32 * 1000 + 32: return launch_wx3_sized<32, 32>(p, stream, dry);

@@ -16,7 +16,6 @@
 // Activations are split while the input tile is staged into LDS (tile.h: three [pixel][CIN + 8] bf16 planes); weights
 // are split once on the host (sbc_pack_conv_weight_split) into B-operand fragment order
 //       [tap][CIN/16][COUT/32][3 terms][64 lanes][8 bf16]:  lane l holds w[n*32 + (l&31)][g*16 + 8*(l>>5) + j].
-#include <stdlib.h>
 #include "conv_epilogue.h"
 
 namespace sbc {
@@ -317,10 +316,8 @@ static int launch_sized(const ConvParams& p, hipStream_t stream, bool dry) {
         return staged > epi ? staged : epi;
     };
     auto good = [&](int tm) { return fits(tm) && px >= (long)tm * 512 && lds_of(tm) <= 80 * 1024; };
-    static const int force = getenv("SBC_TILE") ? atoi(getenv("SBC_TILE")) : 0;     // tuning aid
     int tm = 0;
-    if (force && fits(force)) tm = force;
-    else if ((p.flags & SBC_EPI_MOMENTS_OUT) && !good(256)) {
+    if ((p.flags & SBC_EPI_MOMENTS_OUT) && !good(256)) {
         // tile moments come out of the 256-thread variants (whole 128-pixel tiles per pass): never the 64-pixel tile
         SBC_REQUIRE(COUT == 32 && fits(128), "conv: SBC_EPI_MOMENTS_OUT on the direct kernel needs 32 output channels and 128-pixel tiles (%dx%d)", p.H, p.W);
         tm = 128;

@@ -14,19 +14,12 @@ namespace sbc {
 
 // 16-byte accesses for activations.  Rounds 1-3 made all of them non-temporal ("touched once per kernel").  Round 4 measured it
 // (DESIGN.md section 13.6): a tensor is read by the NEXT launch, usually out of L2 / the 256 MB MALL, so
-//   * loads are plain (cached) loads now: sustained two-stream step 5.05 -> 5.00 ms (-DSBC_NT_LD restores the hint);
+//   * loads are plain (cached) loads now: sustained two-stream step 5.05 -> 5.00 ms;
 //   * stores of the kernels that write whole 128-byte lines per thread group (Winograd, statistics, ...) stay non-temporal (plain:
 //     5.05 -> 5.05, and with the loads plain as well 5.32-5.37 against 5.21 in the first A/B);
 //   * stores of the direct kernels, which write lines in two pieces, are plain: st_out below.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld_stream(const float* p) {
-#ifndef SBC_NT_LD
-    return *reinterpret_cast<const float4*>(p);
-#else
-    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-#endif
-}
+__device__ __forceinline__ float4 ld_stream(const float* p) { return *reinterpret_cast<const float4*>(p); }
 // Output store of the direct kernels (conv_pair, conv_pool, conv_dp, conv_res): a wave writes 64 of a pixel's 128 or 256 bytes, the
 // wave with the other output channels the rest a little later.  As plain (cached) stores the pieces meet in L2 and reach memory as
 // whole lines; as non-temporal stores they did not: WRITE_SIZE 308 MB for a 223 MB tensor (pair), 279 (CRP stage), 276 (ResidualBlock),
@@ -34,12 +27,8 @@ __device__ __forceinline__ float4 ld_stream(const float* p) {
 // write whole lines per thread group and keep st_stream: with plain stores everywhere the step was 5.32-5.37.)
 __device__ __forceinline__ void st_out(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ void st_stream(float* p, float4 v) {
-#if defined(SBC_NO_STREAM) || defined(SBC_PLAIN_ST)
-    *reinterpret_cast<float4*>(p) = v;
-#else
     f32x4 t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w;
     __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(p));
-#endif
 }
 
 // conv_mode f16x2 (SBC_CONV_F16X2): activations enter the matrix cores as x * act_scale split into two fp16 terms.  act_scale is a
@@ -365,7 +354,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // operand read from the fp16 half just written.  Four vector instructions per pair of values.
 // h, l: the two values' terms packed low | high, as the matrix instructions take them.
 // HAZARD: hipcc does not look inside inline assembly, so it inserts none of the wait states a vector-ALU write needs before a
-// MATRIX instruction reads the register.  Where split terms feed v_mfma_* directly from registers (conv_wx3.hip, conv_wp.hip) the
+// MATRIX instruction reads the register.  Where split terms feed v_mfma_* directly from registers (conv_wx3.hip) the
 // caller puts split_f16x2_settle() between the last split and the first matrix instruction: without it one instantiation (128 ->
 // 64, two output blocks per phase), in which nothing else happened to sit between the two, multiplied a stale high half -- results
 // off by 3e-4 ... 0.5, correct at -O1 and with the two wait states.  Terms that go through LDS first (conv_x3, conv_pair) are safe.
@@ -375,17 +364,6 @@ __device__ __forceinline__ void split_f16x2_settle(uint4& h, uint4& l) {
 // Four values at a time: the two high terms are complete before the first low term reads them, so no instruction reads a
 // register in the slot right behind a 16-bit (partial) write of it.
 __device__ __forceinline__ void split_f16x2(float4 x, float s, uint2& h, uint2& l) {
-#ifdef SBC_F16X2_UNSCALED   // timing aid (tools/): the three-instruction split of round 3, right only while every act_scale is 1
-    asm("v_cvt_pk_f16_f32 %0, %2, %3\n\tv_cvt_pk_f16_f32 %1, %4, %5" : "=&v"(h.x), "=&v"(h.y) : "v"(x.x), "v"(x.y), "v"(x.z), "v"(x.w));
-    asm("v_fma_mixlo_f16 %0, %2, 1.0, -%4 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %1, %3, 1.0, -%5 op_sel:[0,0,0] op_sel_hi:[0,0,1]"
-        : "=&v"(l.x), "=&v"(l.y) : "v"(x.x), "v"(x.z), "v"(h.x), "v"(h.y));
-    asm("v_fma_mixhi_f16 %0, %2, 1.0, -%4 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %1, %3, 1.0, -%5 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "+v"(l.x), "+v"(l.y) : "v"(x.y), "v"(x.w), "v"(h.x), "v"(h.y));
-    (void)s;
-    return;
-#endif
     asm("v_fma_mixlo_f16 %0, %4, %8, 0 op_sel_hi:[0,0,0]\n\t"
         "v_fma_mixlo_f16 %1, %6, %8, 0 op_sel_hi:[0,0,0]\n\t"
         "v_fma_mixhi_f16 %0, %5, %8, 0 op_sel_hi:[0,0,0]\n\t"
@@ -504,7 +482,7 @@ __device__ __forceinline__ float4 xor16_4(float4 v) { return make_float4(xor16(v
 
 // Producer side, 256 threads, 32 channels: thread (tid >> 3, tid & 7) holds four pixels of channel quad tid & 7 (any four:
 // together the threads cover the tile's 128 pixels once).  `red`: LDS scratch of 8 * 8 * 8 floats that nobody else touches;
-// `pm_tile`: this tile's [32][2] output.  Contains one workgroup barrier (conv_wsp.hip calls the two halves around its own).
+// `pm_tile`: this tile's [32][2] output.  Contains one workgroup barrier.
 __device__ __forceinline__ void tile_moments_partials32(const float4 (&v)[4], float* red, int tid) {
     float4 mean, m2;
     mean.x = ((v[0].x + v[1].x) + (v[2].x + v[3].x)) * 0.25f; mean.y = ((v[0].y + v[1].y) + (v[2].y + v[3].y)) * 0.25f;

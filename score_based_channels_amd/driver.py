@@ -21,6 +21,9 @@ DEFAULT_USE_GRAPH = False
 # how long a host thread of run_concurrently waits for its partner thread to have QUEUED its launches (not for the GPU): a leader
 # that hangs inside a runtime call after a device fault must surface as an error of the follower, not as a join() that never returns
 HOST_WAIT_S = 600
+# sub-batches of at most this many pixels (T Nt Nr; 2048 trajectories of a 64 x 16 array) run their streams at half grid width and
+# lagged: larger ones fill the chip on their own (run_concurrently has the measurements)
+STREAM_SMALL_PX = 1 << 21
 
 
 def resolve_launch_mode(args):
@@ -101,7 +104,7 @@ def run_concurrently(batches, streams, n_steps, use_graph=False):
     # (... and small sub-batches only: at 10 200 trajectories per stream every launch fills the chip for a millisecond, the streams
     # gain nothing from each other and half-width grids cost 20 % -- 74.6 against 62.1 ms per step of the 20 400-trajectory workload;
     # sustained gain +2.3 % at 1275 trajectories per stream, +0.9 % at 1700, +0.5 % at 2550 where a 20-step segment already loses 1 %)
-    small = max(b.T * b.nt * b.nr for b in batches) <= int(os.environ.get('SBC_STREAM_SMALL_PX', 1 << 21))   # (the variable: A/B aid)
+    small = max(b.T * b.nt * b.nr for b in batches) <= STREAM_SMALL_PX
     # (the width is a field of each batch's plans -- sbc_plan_set_persistent_cus -- not process state: concurrent calls on other host
     # threads or devices do not see it, and it is reset in the `finally` below whatever happens in between)
     half = torch.cuda.get_device_properties(dev).multi_processor_count // 2 if (not use_graph and small) else 0
@@ -109,7 +112,7 @@ def run_concurrently(batches, streams, n_steps, use_graph=False):
     # ... and every second stream walks the schedule ~0.45 of a step behind its neighbour (AldBatch.run_leading / run_following: the
     # lag is the head of the leader's first step, run alone; ~4 % of every step after it)
     lag = (not use_graph and small and n_steps >= int(os.environ.get('SBC_STREAM_LAG_MIN_STEPS', '2'))       # (the variable: tests)
-           and not os.environ.get('SBC_NO_STREAM_LAG') and not any(b.net.overlap or b.uses_lanes for b in batches))
+           and not any(b.net.overlap or b.uses_lanes for b in batches))
     # pair (2j, 2j + 1): two device events (leader's head done; leader done) and the host flags that say they have been RECORDED --
     # a stream that waits for an event nobody has recorded yet does not wait at all
     class _Pair:

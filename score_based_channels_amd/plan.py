@@ -20,7 +20,6 @@ Fusion rules (reference lines in brackets):
   * ``h = 2x - 1`` [ncsnv2.py:270-273] lives in the begin conv; normalizer -> ELU -> end_conv -> / sigma
     [ncsnv2.py:291-298] is one kernel.
 """
-import os
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -337,8 +336,6 @@ PAIR_SHAPES_F16W = ((32, 16), (32, 32), (32, 64), (64, 16), (64, 32))
 def down_fusable(h, w, cin, cout):
     """Downsampling ResidualBlocks SBC_OP_CONV_DOWN takes: 32 -> 64 channels at 16-pixel rows, 64 -> 64 at 8 (res2.0 / res3.0 of a
     64 x 16 array), heights that are multiples of 16."""
-    if os.environ.get('SBC_NO_CONV_DOWN'):           # A/B aid: pooled Winograd convolution + 1x1 shortcut launch
-        return False
     return h % 16 == 0 and ((w == 16 and cin == 32 and cout == 64) or (w == 8 and cin == 64 and cout == 64))
 
 
@@ -423,41 +420,29 @@ def chain_fusable(h, w, c, kind=CHAIN_RCU):
     """Shapes SBC_OP_CHAIN takes: 8 x 2 samples of 64 or 128 channels, 16 x 4 samples of 64 channels (the two lowest levels of a
     64 x 16 array), and 32 x 8 samples of 32 or 64 channels (a wave holds half a sample there; ResidualBlocks are left to their own
     launches at that size: no gain measured)."""
-    if os.environ.get('SBC_NO_CHAIN'):               # A/B aid: every convolution and max pool of those levels as its own launch
-        return False
     if h == 16 and w == 4 and c == 64:
-        return not os.environ.get('SBC_NO_CHAIN4')   # A/B aid: the 16 x 4 level unfused
+        return True
     if h == 32 and w == 8 and c in (32, 64):
-        # (the kernel also takes ResidualBlocks there -- res2.1 -- but measured no gain over its two Winograd launches with folded
-        # statistics: 4.26-4.32 against 4.24-4.25 ms per two-stream step; SBC_CHAIN8_RES=1 plans it, Python plans only)
-        if kind == CHAIN_RES:
-            return bool(os.environ.get('SBC_CHAIN8_RES')) and not os.environ.get('SBC_NO_CHAIN8')
-        if kind == CHAIN_CRP and os.environ.get('SBC_NO_CHAIN8_CRP'):      # A/B aid: refine4's CRP as max pool + convolution launches
-            return False
-        return not os.environ.get('SBC_NO_CHAIN8')                         # A/B aid: the 32 x 8 level unfused
+        # (the kernel also takes ResidualBlocks there -- res2.1 -- through the ABI, but measured no gain over its two Winograd launches
+        # with folded statistics: 4.26-4.32 against 4.24-4.25 ms per two-stream step; the plan does not use it)
+        return kind != CHAIN_RES
     return h == 8 and w == 2 and c in (64, 128)
 
 
 def end_fusable(h, w, c):
     """Shapes whose normalizer statistics the END_CONV launch forms itself (PRO_NORM_SELF): 32 channels, 1024 pixels (the
     normalised sample of a 64 x 16 array fills the LDS of a CU)."""
-    if os.environ.get('SBC_NO_END_SELF'):            # A/B aid: statistics record + end convolution as separate launches
-        return False
     return c == 32 and h * w == 1024
 
 
 def res_fusable(h, w, cin, cout, resample, dilation):
     """ResidualBlocks SBC_OP_RES_BLOCK takes: 32 -> 32 channels, no resampling or dilation, 64 x 16 samples (two fp16 operand planes
     of a whole sample fill the LDS of a CU)."""
-    if os.environ.get('SBC_NO_RES_BLOCK'):           # A/B aid: the two convolutions and the statistics record as separate launches
-        return False
     return cin == 32 and cout == 32 and resample is None and dilation is None and h == 64 and w == 16
 
 
 def pool_fusable(h, w, c):
     """Shapes SBC_OP_CONV_POOL takes (a CRP stage as one launch): 32 channels, 16-pixel rows, heights that are multiples of 8."""
-    if os.environ.get('SBC_NO_CONV_POOL'):           # A/B aid: max pool + convolution as separate launches
-        return False
     return c == 32 and w == 16 and h % 8 == 0
 
 

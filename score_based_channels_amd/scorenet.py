@@ -53,8 +53,8 @@ DEFAULT_FUSE_DOWN = True
 DEFAULT_FUSE_END = True
 # Small batches (a rank's share when a test_score run is sharded over several GPUs): the decoder's skip branches on launch lanes of
 # their own beside the latency-bound low-resolution launches (plan.hoist_skip_branches; identical results).  Batches of at most this
-# many 64 x 16-equivalent trajectories (B Nt Nr / 1024) take that plan; SBC_SKIP_OVERLAP_MAX_T overrides the number, SBC_NO_SKIP_OVERLAP=1
-# turns the plan off (A/B aids)
+# many 64 x 16-equivalent trajectories (B Nt Nr / 1024) take that plan
+# (ScoreNet(skip_overlap=False) turns it off).
 SKIP_OVERLAP_MAX_T = 600
 
 
@@ -99,8 +99,6 @@ class ScoreNet:
         # writes (plan.py `stats`): the statistics launches of those tensors read a few KB per sample instead of the tensor.
         # Needs the Winograd split kernels (not conv_mode 'f32').
         self.fold_stats = (DEFAULT_FOLD_STATS if fold_stats is None else bool(fold_stats)) and conv_mode != 'f32'
-        if os.environ.get('SBC_NO_WX3'):          # (A/B switch of the library: no Winograd split kernel, hence nobody to write tile moments)
-            self.fold_stats = False
         # fuse_pairs: RCU blocks (act -> conv -> act -> conv, + x; layers.py:126-134; shapes: plan.PAIR_SHAPES*) are ONE launch that keeps
         # the intermediate tensor in LDS (csrc/conv_pair.hip); the kernel reads the fp16 weight forms of 'f16x2' / 'f16w'
         self.fuse_pairs = (DEFAULT_FUSE_PAIRS if fuse_pairs is None else bool(fuse_pairs)) and conv_mode in ('f16x2', 'f16w')
@@ -267,9 +265,9 @@ class ScoreNet:
     # --- binding ----------------------------------------------------------------------------------
     def skip_overlap_for(self, B, nt, nr):
         """Does a batch of ``B`` ``nt x nr`` arrays take the plan with the skip branches on their own launch lanes?  (``B`` None: no.)"""
-        if B is None or self.overlap or not self.skip_overlap or os.environ.get('SBC_NO_SKIP_OVERLAP'):
+        if B is None or self.overlap or not self.skip_overlap:
             return False
-        return B * nt * nr <= 1024 * int(os.environ.get('SBC_SKIP_OVERLAP_MAX_T', SKIP_OVERLAP_MAX_T))
+        return B * nt * nr <= 1024 * SKIP_OVERLAP_MAX_T
 
     def score_plan(self, nt, nr, B=None, lanes=None):
         """The launch plan of one score evaluation at ``nt x nr``; ``B`` (the batch it will be bound for) selects the small-batch

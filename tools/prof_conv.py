@@ -59,39 +59,7 @@ e1.record(); torch.cuda.synchronize()
 us = e0.elapsed_time(e1) / a.iters * 1e3
 fl = 2.0 * k * k * cin * cout * B * H * W
 by = 4.0 * B * H * W * (cin + cout * (1 if a.no_res else 2))
-if os.environ.get('WINO_TIMING'):
-    dbg = torch.zeros(4096 * 4 * 6, device='cuda'); op.up = dbg.data_ptr()
-    _lib.check(h.sbc_op_launch(C.byref(op), None)); torch.cuda.synchronize()
-    d = dbg.view(4096, 4, 6).cpu().numpy()
-    names = ['stage', 'barrier', 'K loop', 'T write', 'barrier2', 'finish']
-    print('wave 0 cycles/WG (mean):', {n: int(d[:, 0, i].mean()) for i, n in enumerate(names)}, 'sum', int(d[:, 0].sum(1).mean()))
-if os.environ.get('WP_TIMING'):
-    dbg = torch.zeros(256 * 10, device='cuda', dtype=torch.int64); op.up = dbg.data_ptr()
-    _lib.check(h.sbc_op_launch(C.byref(op), None)); torch.cuda.synchronize()
-    d = dbg.view(256, 10).cpu().numpy().astype(np.float64)
-    d = d[d[:, 9] > 0]
-    names = ['issue', 'V-form+MFMA', 'barrier1', 'ex write', 'commit', 'barrier2', 'last finish', 'finish']
-    nb = d[:, 9].mean()
-    print('conv_wp wave 0: blocks per WG %.1f; cycles per block (mean over WGs):' % nb,
-          {n: int((d[:, i] / d[:, 9]).mean()) for i, n in enumerate(names)}, 'loop total per block', int((d[:, 8] / d[:, 9]).mean()))
 if os.environ.get('DUMP'):
     _lib.check(h.sbc_op_launch(C.byref(op), None)); torch.cuda.synchronize()
     np.save(os.environ['DUMP'], out.cpu().numpy())
-if os.environ.get('WX3_TIMING'):
-    nwg = (B * H * W + 127) // 128
-    dbg = torch.zeros(nwg * 8, device='cuda', dtype=torch.int64); op.up = dbg.data_ptr()
-    _lib.check(h.sbc_op_launch(C.byref(op), None)); torch.cuda.synchronize()
-    d = dbg.view(nwg, 8).cpu().numpy()
-    t = d[:, :7].astype(np.float64) * 0.01            # us (100 MHz)
-    t0 = t[:, 0].min()
-    names = ['issue loads', 'wait+commit', 'barrier', 'K loop', 'T write+bar', 'finish(last blk)']
-    ph = np.diff(t, axis=1)
-    print('WGs', nwg, 'span %.1f us' % (t[:, 6].max() - t0), 'mean WG life %.2f us' % (t[:, 6] - t[:, 0]).mean())
-    print('  mean us per phase:', {n: round(float(ph[:, i].mean()), 2) for i, n in enumerate(names)})
-    hw = d[:, 7]; cu = ((hw >> 32) & 0xf) * 1000 + ((hw >> 13) & 7) * 100 + ((hw >> 12) & 1) * 50 + ((hw >> 8) & 0xf)
-    ucu = np.unique(cu); print('  distinct CUs', len(ucu), 'WGs per CU mean', nwg / len(ucu))
-    # average number of WGs alive per CU over the span
-    alive = (t[:, 6] - t[:, 0]).sum() / len(ucu) / (t[:, 6].max() - t0)
-    print('  mean concurrent WGs per CU %.2f' % alive)
-    order = np.argsort(t[:, 0]); print('  start times (us) of WGs by rank: ', [round(float(t[order[i], 0] - t0), 1) for i in (0, nwg // 4, nwg // 2, 3 * nwg // 4, nwg - 1)])
-print('%s %s tile=%s: %.1f us  %.1f TF(direct-equivalent)  %.2f TB/s(algorithmic)' % (a.mode, a.shape, os.environ.get('SBC_TILE', 'auto'), us, fl / us / 1e6, by / us / 1e6))
+print('%s %s: %.1f us  %.1f TF(direct-equivalent)  %.2f TB/s(algorithmic)' % (a.mode, a.shape, us, fl / us / 1e6, by / us / 1e6))

@@ -1,5 +1,5 @@
 """Performance triage helper (not part of the product): time one 64 -> 64 3x3 SBC_OP_CONV launch in conv_mode f16x2 -- the direct
-persistent kernel (csrc/conv_dp.hip), or with SBC_NO_CONV_DP=1 in the environment the Winograd kernel it replaces.
+persistent kernel (csrc/conv_dp.hip).
 usage: prof_dp.py [B H W] [--stage elu|elu_res|crp2|plain|norm]   (norm: InstanceNorm++ prologue + ELU + tile-moment output, the NM instantiation)"""
 import argparse, ctypes as C, os, sys
 import numpy as np
@@ -40,12 +40,4 @@ run(3); torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); run(a.iters); e1.record(); torch.cuda.synchronize()
 t = e0.elapsed_time(e1) / a.iters * 1e3
-which = 'conv_wx3' if os.environ.get('SBC_NO_CONV_DP') else 'conv_dp'
-if 'pt' in os.environ.get('SBC_LIB_PATH', '') and which == 'conv_dp':
-    dbg = torch.zeros(10, dtype=torch.int64, device='cuda'); cv.aux = dbg.data_ptr()
-    run(1); torch.cuda.synchronize()
-    v = dbg.tolist()
-    names = ['tile wait', 'barrier', 'convert', 'barrier', 'K loop', 'load wait', 'store']
-    tot = sum(v[:7]) or 1
-    print('wave 0, cycles per phase: ' + ', '.join('%s %.1f%%' % (names[i], 100.0 * v[i] / tot) for i in range(7)), '| per WG %.0f' % (tot / (8 * int(os.environ.get('SBC_DP_WGS', 64)))))
-print('%s %s x %d %s: %.1f us' % (which, a.shape, CH, a.stage, t))
+print('conv_dp %s x %d %s: %.1f us' % (a.shape, CH, a.stage, t))

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Stand-alone timing of SBC_OP_CONV_PAIR / SBC_OP_CONV_POOL at the full-resolution level (64x16, 32 channels) on the GPU box:
-hipEvent average over back-to-back launches.  A/B switches of csrc/conv_pair.hip are read from the environment by the library
-(SBC_NO_PAIR_ROLL, SBC_NO_PAIR_P3).
+hipEvent average over back-to-back launches.
 
     python tools/prof_pair.py [B=1700] [reps=50]
 """
@@ -47,8 +46,7 @@ def main():
         us = e0.elapsed_time(e1) / reps * 1e3
         nconv = 2 if name == 'pair' else 1
         flops = nconv * 2.0 * B * H * W * 9 * Cc * Cc
-        print('%s 64x16 C=32 B=%d [%s]: %.1f us per launch, %.0f TFLOP/s algorithmic' % (
-            name, B, ' '.join(k for k in ('SBC_NO_PAIR_ROLL', 'SBC_NO_PAIR_P3') if os.environ.get(k)) or 'default', us, flops / us / 1e6))
+        print('%s 64x16 C=32 B=%d: %.1f us per launch, %.0f TFLOP/s algorithmic' % (name, B, us, flops / us / 1e6))
 
 
 if __name__ == '__main__':

@@ -43,14 +43,6 @@ def timeit(ops):
     e0.record(); run(ops, a.iters); e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / a.iters * 1e3
 tp, tm, tc = timeit([pool]), timeit([mp]), timeit([cv])
-if 'pt' in os.environ.get('SBC_LIB_PATH', ''):
-    dbg = torch.zeros(10, dtype=torch.int64, device='cuda'); pool.aux = dbg.data_ptr()
-    run([pool], 1); torch.cuda.synchronize()
-    v = dbg.tolist()
-    names = ['barrier', 'dma issue', 'convert', 'load wait', 'barrier', 'K loop', 'residual wait', 'store']
-    for lo, who in ((0, 'conversion wave 0'), (4, 'matrix wave 0')):
-        tot = sum(v[lo:lo + 4]) or 1
-        print('%s, cycles per phase: ' % who + ', '.join('%s %.1f%%' % (names[lo + i], 100.0 * v[lo + i] / tot) for i in range(4)), '| per WG %.0f' % (tot / 256))
 err = float((out - out2).abs().max() / out2.abs().max())
 by = 4.0 * B * H * W * 32
 print('%s %s stage %s: fused %.1f us, max pool %.1f us + convolution %.1f us = %.1f us; max deviation %.2e'

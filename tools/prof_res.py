@@ -1,7 +1,5 @@
 """Performance triage helper (not part of the product): time one SBC_OP_RES_BLOCK launch (a whole ResidualBlock at 64x16) against the
-convolution -> statistics -> convolution launches it replaces.   usage: prof_res.py [B]
-With a -DSBC_RES_TIMELINE build (tools/build_variant.sh res_tl conv_res.hip -DSBC_RES_TIMELINE; SBC_LIB_PATH=tools/var/libsbc_res_tl.so) it also
-prints the per-wave timeline of three samples of workgroup 0."""
+convolution -> statistics -> convolution launches it replaces.   usage: prof_res.py [B]"""
 import argparse, ctypes as C, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -44,25 +42,5 @@ def timeit(ops):
     e0.record(); run(ops, a.iters); e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / a.iters * 1e3
 tr, t3 = timeit([res]), timeit([c1, st, c2])
-if 'tl' in os.path.basename(os.environ.get('SBC_LIB_PATH', '')):
-    # SBC_RES_TIMELINE build: block 0's eight waves stamp 12 points of every sample
-    nit = (B + 255) // 256 + 1
-    dbg = torch.zeros(nit * 8 * 16, dtype=torch.int64, device='cuda')
-    res.aux, res.flags = dbg.data_ptr(), P.CONV_F16X2
-    run([res], 1); torch.cuda.synchronize()
-    v = dbg.view(nit, 8, 16).cpu().numpy()
-    names = ['F end', 'top barrier', 'A end', 'A barrier', 'conv1 end', 'moments end', 'stats barrier 1', 'stats barrier 2', 'D end', 'D barrier', 'conv2 end', 'F end']
-    its = [i for i in range(1, nit) if v[i, :, 11].min() > 0]
-    for it in its[1:4]:
-        t0 = v[it, :, 1].min()
-        print('sample %d of block 0 (clock ticks since the top barrier opened; min .. max over the 8 waves)' % it)
-        for k in range(1, 12):
-            print('   %-16s %7d .. %7d' % (names[k], v[it, :, k].min() - t0, v[it, :, k].max() - t0))
-        if it == its[2]:
-            print('   per wave (hf, sub) = wave & 1, wave >> 1; clock ticks of every stamp (the last four: F sums formed, next x requested, stores issued, F end):')
-            for w in range(8):
-                print('     wave %d: ' % w + ' '.join('%6d' % (v[it, w, k] - t0) for k in (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 13, 14, 11)))
-        if it + 1 < nit and v[it + 1, :, 1].min() > 0:
-            print('   %-16s %7d' % ('next top barrier', v[it + 1, :, 1].min() - t0))
 err = float((out - out2).abs().max() / out2.abs().max())
 print('B = %d: fused ResidualBlock %.1f us; conv + statistics + conv %.1f us; max deviation %.2e' % (B, tr, t3, err))
