@@ -345,8 +345,10 @@ typedef struct sbc_endconv {
  * SBC_OP_MEASURE reads Htrue and P and writes Y; its `noise` is [B][Np][Nr] and `meas_scale[b]` =
  * float32(sqrt(local_noise)).
  * Constraints of SBC_OP_LANGEVIN (checked, SBC_ERR_INVALID otherwise): Nr is EVEN -- the update takes the elements of a row in
- * adjacent pairs (one Philox block, one pilot value, 16-byte accesses) -- and X, score, Y, Htrue and noise are 16-byte aligned
- * (Nt * Nr even keeps every per-trajectory slice aligned too).  The score network itself needs Nt, Nr multiples of 8.
+ * adjacent pairs (one Philox block, one pilot value, 16-byte accesses) -- and X, score, P, Y, Htrue and noise are 16-byte aligned
+ * (Nt * Nr even keeps every per-trajectory slice aligned too; P is copied 16 bytes at a time where its rows are staged on chip).
+ * Every refusal names the field; sbc_plan_create makes the same checks of LANGEVIN, MEASURE and STEP_INC records as sbc_op_launch.
+ * The score network itself needs Nt, Nr multiples of 8.
  */
 typedef struct sbc_langevin {
     float* X;

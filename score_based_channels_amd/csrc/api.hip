@@ -515,6 +515,8 @@ int sbc_plan_create(const sbc_op* ops, int32_t n_ops, sbc_plan** out_plan) {
         else if (po.op.kind == SBC_OP_CONV_DOWN) rc = launch_conv_down(po.op, nullptr, true);
         else if (po.op.kind == SBC_OP_END_CONV) rc = launch_end_conv(po.op, po.ext.endc, nullptr, true);
         else if (po.op.kind == SBC_OP_LANGEVIN) rc = launch_langevin(po.op, po.ext.lang, nullptr, true);
+        else if (po.op.kind == SBC_OP_MEASURE) rc = launch_measure(po.op, po.ext.lang, nullptr, true);
+        else if (po.op.kind == SBC_OP_STEP_INC) rc = launch_step_inc(po.op, nullptr, true);
         if (rc) { delete plan; return rc; }
     }
     // launch lanes (ABI 14): validate the records' lane / event fields, create the streams and events they name

@@ -53,8 +53,8 @@ int launch_inorm_stats(const sbc_op& op, hipStream_t stream);
 int launch_maxpool5(const sbc_op& op, hipStream_t stream);
 int launch_end_conv(const sbc_op& op, const sbc_endconv& ext, hipStream_t stream, bool dry = false);
 int launch_langevin(const sbc_op& op, const sbc_langevin& ext, hipStream_t stream, bool dry = false);
-int launch_measure(const sbc_op& op, const sbc_langevin& ext, hipStream_t stream);
-int launch_step_inc(const sbc_op& op, hipStream_t stream);
+int launch_measure(const sbc_op& op, const sbc_langevin& ext, hipStream_t stream, bool dry = false);
+int launch_step_inc(const sbc_op& op, hipStream_t stream, bool dry = false);
 // training operators (train.hip, train_conv.hip)
 int launch_dsm_perturb(const sbc_op& op, const sbc_dsm& ext, hipStream_t stream);
 int launch_dsm_loss(const sbc_op& op, const sbc_dsm& ext, hipStream_t stream);

@@ -892,20 +892,27 @@ __global__ __launch_bounds__(512) void langevin_tiled_kernel(sbc_langevin a, int
 }
 
 static int check_langevin(const sbc_op& op, const sbc_langevin& a, bool measure) {
-    SBC_REQUIRE(a.P && a.Y && a.Htrue, "langevin/measure: P, Y, Htrue must be set");
-    SBC_REQUIRE(a.Nt > 0 && a.Nr > 0 && a.Np > 0 && op.B > 0, "langevin/measure: bad sizes");
+    const char* who = measure ? "measure" : "langevin";
+    // (one message per field: a host that got a record wrong learns which one)
+    const struct { const char* name; const void* p; bool needed; bool aligned; } ptrs[] = {
+        {"P", a.P, true, true}, {"Y", a.Y, true, true}, {"Htrue", a.Htrue, true, true},
+        {"X", a.X, !measure, true}, {"score", a.score, !measure, true}, {"sched", a.sched, !measure, false},
+        {"nmse", a.nmse, !measure, false}, {"step", a.step, !measure, false}, {"noise", a.noise, false, true},
+        {"meas_scale", a.meas_scale, measure, false}};
+    for (const auto& f : ptrs) SBC_REQUIRE(f.p || !f.needed, "%s: %s must be set", who, f.name);
+    SBC_REQUIRE(a.Nt > 0 && a.Nr > 0 && a.Np > 0, "%s: bad sizes Nt = %d, Nr = %d, Np = %d", who, a.Nt, a.Nr, a.Np);
+    SBC_REQUIRE(op.B > 0, "%s: B = %d must be positive", who, op.B);
     if (!measure) {
-        SBC_REQUIRE(a.X && a.score && a.sched && a.nmse && a.step && a.n_steps > 0,
-                    "langevin: X, score, sched, nmse, step must be set");
+        SBC_REQUIRE(a.n_steps > 0, "langevin: n_steps = %d must be positive", a.n_steps);
         const size_t lds = (size_t)a.Np * a.Nr * sizeof(float2);
         SBC_REQUIRE(lds <= 150 * 1024, "langevin: Nr=%d Np=%d needs %zu bytes of LDS", a.Nr, a.Np, lds);
         // the update loop takes the elements of a row in adjacent PAIRS (one Philox block, one pilot value, 16-byte accesses):
-        // a pair must not straddle two rows, and every per-trajectory tensor must start on a 16-byte boundary
+        // a pair must not straddle two rows, and every per-trajectory tensor must start on a 16-byte boundary -- P too: its rows
+        // are copied into LDS 16 bytes at a time when they fit (langevin_kernel, p_in_lds)
         SBC_REQUIRE(a.Nr % 2 == 0, "langevin: Nr = %d must be even (elements are updated in adjacent pairs of a row)", a.Nr);
-        SBC_REQUIRE(!(((uintptr_t)a.X | (uintptr_t)a.score | (uintptr_t)a.Y | (uintptr_t)a.Htrue | (uintptr_t)a.noise) & 15),
-                    "langevin: X, score, Y, Htrue and noise must be 16-byte aligned");
-    } else {
-        SBC_REQUIRE(a.meas_scale, "measure: meas_scale must be set");
+        for (const auto& f : ptrs)
+            SBC_REQUIRE(!f.aligned || !((uintptr_t)f.p & 15),
+                        "langevin: %s must be 16-byte aligned (as X, score, P, Y, Htrue and noise all must)", f.name);
     }
     return SBC_OK;
 }
@@ -958,9 +965,9 @@ __global__ __launch_bounds__(256) void measure_kernel(sbc_langevin a, int B) {
     }
 }
 
-int launch_measure(const sbc_op& op, const sbc_langevin& a, hipStream_t stream) {
+int launch_measure(const sbc_op& op, const sbc_langevin& a, hipStream_t stream, bool dry) {
     const int rc = check_langevin(op, a, true);
-    if (rc) return rc;
+    if (rc || dry) return rc;
     hipLaunchKernelGGL(measure_kernel, dim3(op.B), dim3(256), 0, stream, a, op.B);
     SBC_CHECK_HIP(hipGetLastError());
     return SBC_OK;
@@ -969,8 +976,9 @@ int launch_measure(const sbc_op& op, const sbc_langevin& a, hipStream_t stream) 
 // ------------------------------------------------------------------------------------------------ step counter
 __global__ void step_inc_kernel(int* step) { *step += 1; }
 
-int launch_step_inc(const sbc_op& op, hipStream_t stream) {
+int launch_step_inc(const sbc_op& op, hipStream_t stream, bool dry) {
     SBC_REQUIRE(op.out, "step_inc: out (device int32 counter) must be set");
+    if (dry) return SBC_OK;
     hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, stream, (int*)op.out);
     SBC_CHECK_HIP(hipGetLastError());
     return SBC_OK;
