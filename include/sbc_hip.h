@@ -589,6 +589,60 @@ typedef struct sbc_ls_desc {
 } sbc_ls_desc;
 int sbc_ls_regularized(const sbc_ls_desc* desc, void* stream);
 
+/* --- Learned D-AMP (the L-DAMP baseline of Fig. 5c) -----------------------------------------------------------------------------
+ * src/score_based_channels/test_ldamp.py with aux_models.py:62-190 (LDAMP.forward) and aux_unet.py (FlippedNormUnet), in the
+ * configuration train_ldamp.py:41-47 trains: backbone FlippedUNet, one net per unroll (shared_nets = False), chans 16, 3 pools,
+ * Nt x Nr = 64 x 16 (csrc/ldamp.hip).  Per unroll u, with the denoiser D_u(x) = x - unnorm(U_u(norm(x))):
+ *     r = h + (1 / eig1) P^H z;  h = D_u(r);  eps = max(1e-3 max|r|, 1e-5);  h' = D_u(r + eps d);
+ *     div = (1 / eps) mean over the 2048 reals of d (h' - h);  z = Y - P h + z div            (h = 0, z = Y before the first unroll)
+ * Exact fp32 arithmetic, fixed summation orders, no atomics: a sample's result does not depend on its position in the batch or on
+ * B, bit for bit.  Nothing is clamped: a constant re or im plane of r has a zero standard deviation and gives inf / NaN, as in the
+ * reference.  Complex data are interleaved float32 (re, im); all data pointers are DEVICE pointers except where noted.
+ *
+ *   sbc_ldamp_create            copies the weights of n_nets denoisers from HOST tensors named as in the reference's state_dict,
+ *                               "update_nets.<u>.unet.<...>" (19 per net, torch layouts; every name and element count is checked), to the
+ *                               current device.  Synchronises (hipMemcpy).  The handle is bound to that device.
+ *   sbc_ldamp_workspace_floats  float32 elements of `workspace` a run of B samples and num_unrolls unrolls needs (sbc_ldamp_denoise of B
+ *                               images: the same with num_unrolls = 0); -1 on a negative argument.
+ *   sbc_ldamp_denoise           out = D_net(r) for B images r [B][64][16][2]; asynchronous on `stream`.
+ *   sbc_ldamp_run               num_unrolls (<= n_nets) unrolls for B samples; 19 launches per unroll (+ 1 for the directions, + 1 copy),
+ *                               asynchronous on `stream`.  Every argument is checked before anything is launched; B = 0 launches nothing.
+ *   sbc_ldamp_stage             where stage `stage` of the last call's images lies in its workspace: `offset` floats from the start, as
+ *                               [n_images][channels][height][width] (n_images = B of sbc_ldamp_denoise, 2B of sbc_ldamp_run: image b is
+ *                               the clean, B + b the perturbed evaluation of sample b in the last unroll).  Stages, in order: 0 r (complex
+ *                               [64][16][2]), 1 norm(r), 2/3 first down block (conv 1, conv 2), 4 its pool, 5/6/7 second, 8/9/10 third, 11/12
+ *                               bottleneck, then per up level (transposed conv, conv 1, conv 2): 13/14/15, 16/17/18, 19/20/21, and 22 the
+ *                               norm's (mean_re, std_re, mean_im, std_im).  No stage shares memory with another.
+ *   sbc_debug_ldamp_directions  (synchronous, current device) the direction d [64][16][2] -> HOST that a run without caller directions
+ *                               uses for global sample id `sample` at `unroll` under `seed`: element (t, r) is the pair of N(0,1) draws
+ *                               of one Philox4x32-10 block, counter (t * 16 + r, unroll, sample_lo, sample_hi), key = seed, Box-Muller on
+ *                               words (x, y).  Written by the same kernel a run launches. */
+typedef struct sbc_ldamp sbc_ldamp;
+typedef struct sbc_ldamp_run_desc {
+    const float* Y_herm;       /* [B][Np][16] complex measurements (sample['Y_herm'])                                            */
+    const float* P_herm;       /* [B][Np][64] complex pilots (sample['P_herm'])                                                  */
+    const float* eig1;         /* [B] (sample['eig1'])                                                                           */
+    const float* directions;   /* [num_unrolls][B][64][16][2] random directions, or NULL = drawn on the device from (seed, sample0 + b, u) */
+    const float* Htrue;        /* [B][64][16] complex channels for the NMSE, or NULL                                             */
+    float* H_hat;              /* [B][64][16] complex: the last unroll's h (also the running h between unrolls)                  */
+    float* nmse;               /* [B] ||H_hat - Htrue||^2 / ||Htrue||^2, or NULL                                                 */
+    float* h_log;              /* [num_unrolls][B][64][16] complex h after every unroll, or NULL                                 */
+    float* z_log;              /* [num_unrolls][B][Np][16] complex z after every unroll, or NULL                                 */
+    float* div_log;            /* [num_unrolls][B], or NULL                                                                      */
+    float* eps_log;            /* [num_unrolls][B], or NULL                                                                      */
+    float* workspace;          /* sbc_ldamp_workspace_floats(B, num_unrolls) floats                                              */
+    uint64_t seed;             /* of the device-drawn directions                                                                 */
+    int64_t sample0;           /* global id of sample 0 (sample b draws from stream sample0 + b)                                 */
+    int32_t B, Np, Nt, Nr, num_unrolls;   /* Nt = 64, Nr = 16, 1 <= Np <= 64                                                      */
+} sbc_ldamp_run_desc;
+int sbc_ldamp_create(const sbc_tensor_ref* tensors, int32_t n_tensors, int32_t n_nets, sbc_ldamp** out);
+void sbc_ldamp_destroy(sbc_ldamp* handle);
+int64_t sbc_ldamp_workspace_floats(int32_t B, int32_t num_unrolls);
+int sbc_ldamp_denoise(sbc_ldamp* handle, int32_t net, const float* r, float* out, int32_t B, float* workspace, void* stream);
+int sbc_ldamp_run(sbc_ldamp* handle, const sbc_ldamp_run_desc* desc, void* stream);
+int sbc_ldamp_stage(int32_t stage, int32_t n_images, int64_t* offset, int32_t* channels, int32_t* height, int32_t* width);
+int sbc_debug_ldamp_directions(uint64_t seed, int64_t sample, int32_t unroll, float* out);
+
 /* ---- Environment variables -------------------------------------------------------------------------------------------------
  * Everything the library (csrc/) and the Python host (score_based_channels_amd/) read from the environment, in ONE place.  None of them
  * changes a result beyond the stated tolerance of the tests that set them; they configure the process or are needed by a test or by

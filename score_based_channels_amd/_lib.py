@@ -18,7 +18,9 @@ EXPORTS = ('sbc_abi_version', 'sbc_set_persistent_cus', 'sbc_last_error', 'sbc_d
            'sbc_pack_conv_weight_f16x2', 'sbc_pack_conv_weight_winograd_f16x2', 'sbc_pack_conv_weight_pooled_f16x2', 'sbc_range_flag',
            'sbc_f16x2_calibration_input', 'sbc_f16x2_calibrate', 'sbc_debug_philox4x32', 'sbc_debug_complex_normal',
            'sbc_score_create', 'sbc_score_buffers', 'sbc_score_ops', 'sbc_score_level_source', 'sbc_score_forward',
-           'sbc_score_destroy', 'sbc_wgrad_scratch_floats', 'sbc_l1_lifted_run', 'sbc_ls_regularized')
+           'sbc_score_destroy', 'sbc_wgrad_scratch_floats', 'sbc_l1_lifted_run', 'sbc_ls_regularized',
+           'sbc_ldamp_create', 'sbc_ldamp_destroy', 'sbc_ldamp_workspace_floats', 'sbc_ldamp_denoise', 'sbc_ldamp_run', 'sbc_ldamp_stage',
+           'sbc_debug_ldamp_directions')
 
 
 class SbcError(RuntimeError):
@@ -97,6 +99,14 @@ class sbc_ls_desc(C.Structure):
                 ('B', C.c_int32), ('nP', C.c_int32), ('nH', C.c_int32), ('Nt', C.c_int32), ('Nr', C.c_int32), ('Np', C.c_int32)]
 
 
+# Learned D-AMP (ldamp.py)
+class sbc_ldamp_run_desc(C.Structure):
+    _fields_ = [('Y_herm', C.c_void_p), ('P_herm', C.c_void_p), ('eig1', C.c_void_p), ('directions', C.c_void_p), ('Htrue', C.c_void_p),
+                ('H_hat', C.c_void_p), ('nmse', C.c_void_p), ('h_log', C.c_void_p), ('z_log', C.c_void_p), ('div_log', C.c_void_p),
+                ('eps_log', C.c_void_p), ('workspace', C.c_void_p), ('seed', C.c_uint64), ('sample0', C.c_int64),
+                ('B', C.c_int32), ('Np', C.c_int32), ('Nt', C.c_int32), ('Nr', C.c_int32), ('num_unrolls', C.c_int32)]
+
+
 _lib = None
 
 
@@ -145,6 +155,15 @@ def lib():
     h.sbc_wgrad_scratch_floats.restype = C.c_int64
     h.sbc_l1_lifted_run.argtypes = [C.POINTER(sbc_l1_lifted_desc), C.c_void_p]
     h.sbc_ls_regularized.argtypes = [C.POINTER(sbc_ls_desc), C.c_void_p]
+    h.sbc_ldamp_create.argtypes = [C.POINTER(sbc_tensor_ref), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    h.sbc_ldamp_destroy.argtypes = [C.c_void_p]
+    h.sbc_ldamp_destroy.restype = None
+    h.sbc_ldamp_workspace_floats.argtypes = [C.c_int32, C.c_int32]
+    h.sbc_ldamp_workspace_floats.restype = C.c_int64
+    h.sbc_ldamp_denoise.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    h.sbc_ldamp_run.argtypes = [C.c_void_p, C.POINTER(sbc_ldamp_run_desc), C.c_void_p]
+    h.sbc_ldamp_stage.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    h.sbc_debug_ldamp_directions.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_void_p]
     if h.sbc_abi_version() != ABI_VERSION:
         raise SbcError('libsbc_hip.so ABI %d != expected %d' % (h.sbc_abi_version(), ABI_VERSION))
     _lib = h

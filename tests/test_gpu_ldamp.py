@@ -1,0 +1,263 @@
+"""Learned D-AMP on the GPU (score_based_channels_amd/ldamp.py, csrc/ldamp.hip) against the reference fixtures and the float64 oracle.
+
+The tolerance rule of every comparison here: the fp32 reference itself drifts from float64 (the divergence estimate divides a
+difference of two network outputs by eps ~ 1e-3 max|r|), so for a quantity q let e_ref = error of the fp32 reference (fixture; where
+there is no fixture, the oracle run in fp32) against float64 -- norm-wise per sample, maximum over samples, for tensors; absolute for
+the scalar div -- and require  error(kernel, float64) <= 4 e_ref.  The factor covers another, equally valid fp32 summation order and
+the ~2x scatter of a maximum over four samples.  Every figure is printed before it is asserted.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import ldamp_oracle as O
+from conftest import load_golden
+from score_based_channels_amd import _lib, ldamp
+
+pytestmark = pytest.mark.gpu
+HP = {'backbone': 'FlippedUNet', 'shared_nets': False, 'max_unrolls': 10, 'in_channels': 2}
+FACTOR = 4.0
+
+
+@pytest.fixture(scope='module')
+def weights():
+    return ldamp.seeded_state_dict(int(load_golden('ldamp_unet.npz')['seed_weights']))
+
+
+@pytest.fixture(scope='module')
+def model(weights):
+    return ldamp.LDAMP(HP, device='cuda:0').load_state_dict(weights).eval()
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to('cuda:0')
+
+
+def sample_of(Y, P, eig):
+    return {'Y_herm': dev(Y), 'P_herm': dev(P), 'eig1': dev(eig)}
+
+
+def host_logs(logs):
+    return {k: v.cpu().numpy() for k, v in logs.items()}
+
+
+def check(what, got, ref64, ref32, kind='norm'):
+    f = O.normwise if kind == 'norm' else O.absolute
+    err, e_ref = f(got, ref64), f(ref32, ref64)
+    print('%-28s kernel %.3e   e_ref %.3e   ratio %.2f' % (what, err, e_ref, err / max(e_ref, 1e-300)))
+    return err <= FACTOR * e_ref, (what, err, e_ref)
+
+
+def assert_all(results):
+    bad = [info for ok, info in results if not ok]
+    assert not bad, bad
+
+
+@pytest.mark.parametrize('net', [0, 9])
+def test_one_evaluation(model, weights, net):
+    """net 0 against the reference fixture; net 9 (no fixture) against the oracle, fp32 oracle as the stand-in for the reference"""
+    g = O.golden_unet()
+    got = model.denoise(net, dev(g['r'])).cpu().numpy()
+    if net == 0:
+        ref64, ref32 = g['out64'], g['out32']
+    else:
+        ref64, ref32 = O.denoise(weights, net, g['r'], torch.float64), O.denoise(weights, net, g['r'], torch.float32)
+    assert_all([check('denoise net %d' % net, got, ref64, ref32)])
+
+
+def test_each_layer_kind(model, weights):
+    """Every launch of one evaluation on its own: the stage's input as the kernel left it in the workspace goes through the oracle's layer in
+    float64 and float32; the kernel's output of that stage is held to the rule.  Kinds: first ConvBlock (x -> d0a -> d0), pooled ConvBlock
+    (-> p0 / p1 / p2: the pool is the producer's epilogue), the 8x2 bottleneck (ba, bb), transposed-conv stages (t0, t1, t2), two-source
+    ConvBlocks (u0a, u1a, u2a), and the 1x1 with unnorm and residual (the output)."""
+    g = O.golden_unet()
+    out = model.denoise(0, dev(g['r'])).cpu().numpy()
+    st = {n: model.stage(n).cpu().numpy() for n in ldamp.STAGES}
+    W = lambda k, dt: torch.from_numpy(weights['update_nets.0.unet.' + k]).to(dt)           # noqa: E731
+    T = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt)                       # noqa: E731
+    res = []
+
+    def both(f):
+        with torch.no_grad():
+            return f(torch.float64).numpy(), f(torch.float32).numpy()
+
+    # norm (part of the first launch)
+    r = st['r']
+    planes = np.stack((r[..., 0], r[..., 1]), axis=1)
+    assert np.array_equal(r[..., 0] + 1j * r[..., 1], g['r'])
+    res.append(check('norm', st['x'], *both(lambda dt: O.norm(T(planes, dt))[0])))
+    chain = [('d0a', 'x', 'down_sample_layers.0.layers.0.weight'), ('d0', 'd0a', 'down_sample_layers.0.layers.4.weight'),
+             ('d1a', 'p0', 'down_sample_layers.1.layers.0.weight'), ('d1', 'd1a', 'down_sample_layers.1.layers.4.weight'),
+             ('d2a', 'p1', 'down_sample_layers.2.layers.0.weight'), ('d2', 'd2a', 'down_sample_layers.2.layers.4.weight'),
+             ('ba', 'p2', 'conv.layers.0.weight'), ('bb', 'ba', 'conv.layers.4.weight'),
+             ('u0', 'u0a', 'up_conv.0.layers.4.weight'), ('u1', 'u1a', 'up_conv.1.layers.4.weight'), ('u2', 'u2a', 'up_conv.2.0.layers.4.weight')]
+    for o, i, k in chain:
+        res.append(check('conv half %s -> %s' % (i, o), st[o], *both(lambda dt: O.conv_half(T(st[i], dt), W(k, dt)))))
+    for p, i, k in (('p0', 'd0a', 'down_sample_layers.0.layers.4.weight'), ('p1', 'd1a', 'down_sample_layers.1.layers.4.weight'),
+                    ('p2', 'd2a', 'down_sample_layers.2.layers.4.weight')):
+        res.append(check('pooled conv half %s -> %s' % (i, p), st[p], *both(lambda dt: O.pool(O.conv_half(T(st[i], dt), W(k, dt))))))
+    for t, i, k in (('t0', 'bb', 'up_transpose_conv.0.layers.0.weight'), ('t1', 'u0', 'up_transpose_conv.1.layers.0.weight'),
+                    ('t2', 'u1', 'up_transpose_conv.2.layers.0.weight')):
+        res.append(check('transposed conv %s -> %s' % (i, t), st[t], *both(lambda dt: O.tconv_stage(T(st[i], dt), W(k, dt)))))
+    for o, a, b, k in (('u0a', 't0', 'd2', 'up_conv.0.layers.0.weight'), ('u1a', 't1', 'd1', 'up_conv.1.layers.0.weight'),
+                       ('u2a', 't2', 'd0', 'up_conv.2.0.layers.0.weight')):
+        res.append(check('two-source conv half %s+%s -> %s' % (a, b, o), st[o],
+                         *both(lambda dt: O.conv_half(torch.cat([T(st[a], dt), T(st[b], dt)], dim=1), W(k, dt)))))
+
+    def fin(dt):
+        s = T(st['stat'], dt)
+        mean, std = s[:, [0, 2]][:, :, None, None], s[:, [1, 3]][:, :, None, None]
+        return O.final(T(st['u2'], dt), W('up_conv.2.1.weight', dt), W('up_conv.2.1.bias', dt), mean, std, T(planes, dt))
+    outp = np.stack((out.real, out.imag), axis=1)
+    res.append(check('1x1 + unnorm + residual', outp, *both(fin)))
+    assert_all(res)
+
+
+def test_ten_unrolls_against_the_reference(model):
+    u = O.golden_unroll()
+    H_hat, logs = model(sample_of(u['Y_herm'], u['P_herm'], u['eig1']), 10, directions=u['directions'], return_logs=True, H=dev(u['H_herm_cplx']))
+    L = host_logs(logs)
+    res = []
+    for k in range(10):
+        res.append(check('unroll %d h' % k, L['h'][k], u['h64'][k], u['h32'][k]))
+        res.append(check('unroll %d z' % k, L['z'][k], u['z64'][k], u['z32'][k]))
+        res.append(check('unroll %d div' % k, L['div'][k], u['div64'][k], u['div32'][k], 'abs'))
+        # eps = fp32(1e-3) * max hypot(re, im) of r: three fp32 roundings (r's last, the hypot, the product) on top of r's inherited error,
+        # which the reference's own eps error measures
+        rel = np.max(np.abs(L['eps'][k] / u['eps64'][k] - 1))
+        rel_ref = np.max(np.abs(u['eps32'][k].astype(np.float64) / u['eps64'][k] - 1))
+        print('unroll %d eps                 kernel %.3e   e_ref %.3e' % (k, rel, rel_ref))
+        res.append((rel <= FACTOR * rel_ref + 3 * 2.0 ** -24, ('eps', k, rel, rel_ref)))
+    assert np.array_equal(H_hat.cpu().numpy(), L['h'][9])
+    nm = np.sum(np.abs(L['h'][9] - u['H_herm_cplx']) ** 2, (1, 2)) / np.sum(np.abs(u['H_herm_cplx']) ** 2, (1, 2))
+    assert np.max(np.abs(L['nmse'] / nm - 1)) < 1e-5                  # the kernel's NMSE of its own h (fp32 differences, double sums)
+    assert_all(res)
+
+
+@pytest.mark.parametrize('Np', [1, 12, 38, 64])
+def test_pilot_counts(model, weights, Np):
+    Y, P, eig, _ = O.synthetic_problem(4, Np, 10.0, 21 + Np)
+    d = np.random.default_rng(Np).standard_normal((3, 4, 64, 16, 2)).astype(np.float32)
+    _, logs = model(sample_of(Y, P, eig), 3, directions=d, return_logs=True)
+    L = host_logs(logs)
+    r64, r32 = O.run_oracle(weights, Y, P, eig, d, 3, torch.float64), O.run_oracle(weights, Y, P, eig, d, 3, torch.float32)
+    res = []
+    for k in range(3):
+        res.append(check('Np %d unroll %d h' % (Np, k), L['h'][k], r64['h'][k], r32['h'][k]))
+        res.append(check('Np %d unroll %d z' % (Np, k), L['z'][k], r64['z'][k], r32['z'][k]))
+        res.append(check('Np %d unroll %d div' % (Np, k), L['div'][k], r64['div'][k], r32['div'][k], 'abs'))
+    assert_all(res)
+
+
+def test_batch_size_and_repetition_do_not_change_a_bit(model):
+    Y, P, eig, _ = O.synthetic_problem(100, 38, 5.0, 33)
+    d = np.random.default_rng(8).standard_normal((3, 100, 64, 16, 2)).astype(np.float32)
+    runs = {}
+    for B in (100, 3, 1, 100):
+        _, logs = model(sample_of(Y[:B], P[:B], eig[:B]), 3, directions=d[:, :B], return_logs=True)
+        L = host_logs(logs)
+        if B in runs:
+            assert all(np.array_equal(L[k], runs[B][k]) for k in L), 'a repeated run differs'
+        runs[B] = L
+    assert np.all(np.isfinite(runs[100]['h']))
+    for B in (3, 1):
+        for k in ('h', 'z', 'div', 'eps'):
+            assert np.array_equal(runs[B][k], runs[100][k][:, :B]), (B, k)
+    # the same sample at another position of the batch
+    _, logs = model(sample_of(Y[2:7], P[2:7], eig[2:7]), 3, directions=d[:, 2:7], return_logs=True)
+    L = host_logs(logs)
+    assert all(np.array_equal(L[k], runs[100][k][:, 2:7]) for k in ('h', 'z', 'div', 'eps'))
+
+
+def test_device_directions_and_their_host_replay(model):
+    Y, P, eig, _ = O.synthetic_problem(4, 38, 10.0, 44)
+    ids = np.arange(10, 14)
+    _, logs = model(sample_of(Y, P, eig), 3, seed=5, sample_ids=ids, return_logs=True)
+    L = host_logs(logs)
+    replay = ldamp.replay_directions(5, ids, 3)
+    # the directions the run drew lie behind the evaluations, z and eps in its workspace (include/sbc_hip.h)
+    ws, n = model.last_workspace
+    off, _ = ldamp.stage_layout('stat', 1)
+    start = n * (off + 4) + 4 * (2 * 1024 + 16)
+    used = ws[start:start + replay.size].cpu().numpy().reshape(replay.shape)
+    assert np.array_equal(used, replay)
+    assert abs(replay.mean()) < 0.02 and abs(replay.std() - 1) < 0.02 and np.all(np.isfinite(replay))
+    assert not np.array_equal(replay[0, 0], replay[0, 1]) and not np.array_equal(replay[0, 0], replay[1, 0])
+    assert not np.array_equal(ldamp.replay_directions(6, ids[:1], 1), replay[:1, :1])
+    _, logs2 = model(sample_of(Y, P, eig), 3, directions=replay, return_logs=True)
+    L2 = host_logs(logs2)
+    assert all(np.array_equal(L[k], L2[k]) for k in L)
+    # a sample's draws depend on its global id, not on its position
+    _, logs3 = model(sample_of(Y[1:3], P[1:3], eig[1:3]), 3, seed=5, sample_ids=ids[1:3], return_logs=True)
+    assert np.array_equal(host_logs(logs3)['h'], L['h'][:, 1:3])
+
+
+CLI = ['--synthetic', '--seed', '1', '--noise', 'host', '--snr_range', '0', '20', '--num_channels', '8', '--no_plot']
+
+
+def test_cli_end_to_end_against_the_oracle(tmp_path, monkeypatch):
+    from score_based_channels_amd import test_ldamp as T
+    monkeypatch.chdir(tmp_path)
+    got = T.main(CLI + ['--synthetic_weights', '7'])['nmse_log']
+    sd = ldamp.seeded_state_dict(7)
+    ref = {}
+
+    def oracle(dtype):
+        def f(model, batch, num_unrolls, directions, seed, device):
+            h = O.run_oracle(sd, batch['Y_herm'], batch['P_herm'], batch['eig1'], directions, num_unrolls, dtype)['h'][-1]
+            H = batch['H_herm_cplx']
+            return np.sum(np.abs(h - H) ** 2, (1, 2)) / np.sum(np.abs(H) ** 2, (1, 2))
+        return f
+    for dtype in (torch.float64, torch.float32):           # the same numpy stream: the same data, noise and directions
+        ref[dtype] = T.main(CLI + ['--synthetic_weights', '7'], estimate_fn=oracle(dtype))['nmse_log']
+    assert got.shape == (1, 1, 2, 8) and np.all(np.isfinite(got))
+    res = [check('CLI nmse, SNR point %d' % s, got[0, 0, s], ref[torch.float64][0, 0, s], ref[torch.float32][0, 0, s], 'abs') for s in range(2)]
+    assert_all(res)
+
+
+def test_cli_from_checkpoints(tmp_path, monkeypatch):
+    """Checkpoints written with save_checkpoint under the reference's path pattern give what --synthetic_weights gives."""
+    from score_based_channels_amd import test_ldamp as T
+    from score_based_channels_amd.checkpoint import save_checkpoint
+    monkeypatch.chdir(tmp_path)
+    want = T.main(CLI + ['--synthetic_weights', '7'])['nmse_log']
+    for snr in (0.0, 20.0):
+        path = T.checkpoint_path('CDL-C', snr, 0.6)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        save_checkpoint(path, ldamp.seeded_state_dict(7), T.ldamp_config('CDL-C', 0.6))
+    got = T.main(CLI)['nmse_log']
+    assert np.array_equal(got, want)
+    assert os.path.exists('results/ldamp/train-CDL-C_test-CDL-C/results.pt')
+
+
+def test_rejected_settings_raise(model, weights):
+    for bad in ({'backbone': 'DnCNN'}, {'backbone': 'UNet'}, {'shared_nets': True}):
+        with pytest.raises(ValueError):
+            ldamp.LDAMP(dict(HP, **bad))
+    Y, P, eig, _ = O.synthetic_problem(2, 38, 10.0, 3)
+    with pytest.raises(ValueError, match='geometry'):
+        model(sample_of(Y[:, :, :8], P, eig), 3)
+    with pytest.raises(ValueError, match='num_unrolls'):
+        model(sample_of(Y, P, eig), 11)
+    with pytest.raises(RuntimeError):
+        ldamp.LDAMP(HP)(sample_of(Y, P, eig), 3)                      # no weights
+    short = dict(weights)
+    short.pop('update_nets.9.unet.up_conv.2.1.bias')
+    with pytest.raises(KeyError):
+        ldamp.LDAMP(HP).load_state_dict(short)
+    # the library refuses by itself too, before any launch
+    s = sample_of(Y, P, eig)
+    out = torch.full((2, 64, 16), 7.0, dtype=torch.complex64, device='cuda:0')
+    ws = torch.empty(int(_lib.lib().sbc_ldamp_workspace_floats(2, 3)), device='cuda:0')
+    p = lambda t: C.c_void_p(t.data_ptr())                          # noqa: E731
+    for field, val in (('Nt', 32), ('Nr', 8), ('Np', 65), ('Np', 0), ('num_unrolls', 11), ('B', -1)):
+        kw = dict(Y_herm=p(s['Y_herm']), P_herm=p(s['P_herm']), eig1=p(s['eig1']), H_hat=p(out), workspace=p(ws), B=2, Np=38, Nt=64, Nr=16, num_unrolls=3)
+        kw[field] = val
+        d = _lib.sbc_ldamp_run_desc(**kw)
+        assert _lib.lib().sbc_ldamp_run(model._h, C.byref(d), None) == -1, field
+        assert field in _lib.lib().sbc_last_error().decode()
+    torch.cuda.synchronize()
+    assert torch.all(out == 7.0)
