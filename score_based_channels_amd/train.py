@@ -25,6 +25,22 @@ from . import plan as P
 from .weights import get_sigmas, state_dict_spec
 
 
+WGRAD_TILE = 64           # WG_TM of csrc/train_conv.hip: pixels per tile of conv_wgrad_kernel
+
+
+def untileable_levels(plan):
+    """(H, W) of the convolution inputs of ``plan`` that SBC_OP_CONV_WGRAD refuses (launch_wgrad_t in csrc/train_conv.hip:
+    a tile is whole rows, and either whole tiles make an image or whole images make a tile).  The forward pass takes such
+    shapes, so without this check the refusal would surface as an error out of the middle of a training step."""
+    bad = []
+    for op in plan.ops:
+        if op.kind == P.CONV:
+            h, w = op.src.h, op.src.w
+            if (WGRAD_TILE % w or ((h * w) % WGRAD_TILE and WGRAD_TILE % (h * w))) and (h, w) not in bad:
+                bad.append((h, w))
+    return bad
+
+
 def _ptr(t, offset_elems=0):
     return C.c_void_p(t.data_ptr() + 4 * offset_elems)
 
@@ -63,6 +79,11 @@ class TrainNet:
         # sample index, so a step does not depend on how the batch is split
         self.rank, self.world = int(rank), int(world)
         self.plan = P.build_score_plan(self.ngf, self.nt, self.nr, self.channels, share_slots=False)
+        bad = untileable_levels(self.plan)
+        if bad:
+            raise ValueError('TrainNet: a %dx%d array cannot be trained: its %s level(s) do not tile by the %d pixels of the '
+                             'weight-gradient kernel (every level must have rows that divide %d and an image that is a multiple '
+                             'or a divisor of it)' % (self.nt, self.nr, ', '.join('%dx%d' % hw for hw in bad), WGRAD_TILE, WGRAD_TILE))
         self._layout()
         self._alloc()
         self._plans = {}

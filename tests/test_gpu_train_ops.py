@@ -192,6 +192,11 @@ WGRAD_CASES = [
     (64, 64, 3, 1, 1, 128, 32, 'elu'),
     (128, 128, 3, 4, 1, 32, 8, 'norm_elu'),     # dilation 4 with a real halo (tiles of 8 rows inside a 32-row image)
     (64, 128, 3, 2, 2, 32, 8, 'norm_elu'),
+    # widths of 1 and 2 under dilation (the 16 x 1 and 8 x 2 levels of 128 x 8 and 64 x 16 arrays): only the centre column of taps
+    # reads the image; several images per 64-pixel tile and a partial last tile (48 and 80 pixels)
+    (64, 64, 3, 2, 3, 16, 1, 'norm_elu'),
+    (128, 128, 3, 4, 5, 8, 2, 'norm_elu'),
+    (32, 32, 3, 1, 1, 16, 64, 'norm_elu'),      # 64-pixel rows (a 16 x 64 array): one row per tile
 ]
 
 
@@ -260,7 +265,11 @@ def test_device_weight_packing_matches_host_packer(gpu, cin, cout, k):
 @pytest.mark.parametrize('mode', ['plain', 'elu', 'elu_plus_other', 'elu_in_place'])
 @pytest.mark.parametrize('cin,cout,k,dil,B,H,W', [(32, 64, 1, 1, 2, 64, 16), (32, 64, 3, 1, 2, 64, 16), (64, 128, 3, 2, 5, 8, 2),
                                                    (128, 64, 3, 1, 5, 8, 2), (64, 64, 3, 1, 3, 16, 4), (128, 128, 3, 4, 5, 8, 2),
-                                                   (32, 32, 3, 1, 3, 64, 16)])
+                                                   (32, 32, 3, 1, 3, 64, 16),
+                                                   # widths 1 and 2 (16 x 1: the lowest level of a 128 x 8 array; 2 x 2: of 16 x 16), 16 x 64
+                                                   (64, 128, 3, 2, 3, 16, 1), (128, 128, 3, 4, 3, 16, 1), (128, 64, 3, 1, 3, 16, 1),
+                                                   (128, 128, 3, 1, 5, 2, 2), (64, 128, 3, 2, 5, 2, 2),
+                                                   (32, 32, 3, 1, 2, 16, 64), (32, 64, 1, 1, 2, 16, 64)])
 def test_input_gradient_is_a_conv_with_adjoint_weights(gpu, cin, cout, k, dil, B, H, W, mode):
     """dL/d(conv input) = SBC_OP_CONV(grad, adjoint-packed weight): the route train.py takes for every convolution.  With
     SBC_EPI_ELUGRAD the epilogue also goes back through the forward ELU prologue (times ELU'(x)) and adds the gradient
@@ -437,3 +446,379 @@ def test_adam_ema_matches_torch_optimizer(gpu):
     assert np.max(np.abs(state[2].cpu().numpy() - shadow.numpy())) < 1e-6
     assert rel_err(state[0].cpu().numpy(), opt.state[pt]['exp_avg'].numpy()) < 1e-6
     assert rel_err(state[1].cpu().numpy(), opt.state[pt]['exp_avg_sq'].numpy()) < 1e-6
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The paths the tests above leave out: the forms and arguments train.py actually uses, the shapes of other arrays than 64 x 16
+# (widths of 1 and 2, images of 16 and 4 pixels), exact ties, and inputs that cancel.  Each against float64 of the same operator.
+
+NETWORK_WEIGHTS = [(32, 32, 3), (32, 64, 3), (32, 64, 1), (64, 64, 3), (64, 64, 1), (64, 32, 3), (64, 128, 3), (128, 128, 3),
+                   (128, 64, 3)]                        # every (cin, cout, k) of a packed convolution weight of the network
+
+
+def test_batched_weight_packing_packs_every_entry_of_its_table(gpu):
+    """SBC_OP_PACK_WEIGHT with ``aux`` = a device table (the only form train.py uses): all four forms of every weight shape of the
+    network in ONE launch, at non-zero source and destination offsets; each entry bit-equal to the host packer, and the guard words
+    between the entries untouched."""
+    torch, _lib = gpu
+    from score_based_channels_amd import plan as P
+    from score_based_channels_amd.weights import pack_conv_weight_split, pack_conv_weight_winograd_split
+    rng = np.random.default_rng(77)
+    GUARD, PATTERN = 24, 0x5A5A
+    src, rows, want, s_off, d_off = [], [], [], 12, GUARD
+    for cin, cout, k in NETWORK_WEIGHTS:
+        w = (rng.standard_normal((cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(F32)
+        src.append((s_off, w))
+        wa = np.ascontiguousarray(w[:, :, ::-1, ::-1].transpose(1, 0, 2, 3))
+        for taps, adj in [(k * k, 0), (k * k, 1)] + ([(16, 0), (16, 1)] if k == 3 else []):
+            host = (pack_conv_weight_winograd_split if taps == 16 else pack_conv_weight_split)(wa if adj else w)
+            assert host.size == 3 * cout * cin * taps
+            rows.append((s_off, d_off, cout, cin, taps, adj))
+            want.append((d_off, host.ravel()))
+            d_off += host.size + GUARD
+        s_off += w.size + 20                            # (a multiple of 4 floats, like the flat parameter buffer's offsets)
+    flat = rng.standard_normal(s_off).astype(F32)       # what lies between the weights is not a weight
+    for off, w in src:
+        flat[off:off + w.size] = w.ravel()
+    dflat = _dev(torch, flat)
+    out = torch.full((d_off,), PATTERN, dtype=torch.int16, device='cuda')
+    table = _dev(torch, np.array(rows, np.int32))
+    op = _lib.sbc_op(kind=P.PACK_WEIGHT, B=len(rows), cout=128, cin=128, ksize=3, in_=_p(dflat), out=_p(out), aux=_p(table))
+    _launch(gpu, op)
+    got = out.cpu().numpy().view(np.uint16)
+    covered = np.zeros(d_off, bool)
+    for (off, host), row in zip(want, rows):
+        assert np.array_equal(got[off:off + host.size], host), row
+        covered[off:off + host.size] = True
+    assert (~covered).sum() == GUARD * (len(rows) + 1) and np.all(got[~covered] == PATTERN)
+
+
+def _dsm_reference(s, noise, us, power, B, gs):
+    """dsm.py:19-30 in float64 and d(mean loss * gs)/d(scores)."""
+    us = us.astype(np.float64)[:, None]
+    d = s.astype(np.float64) + noise.astype(np.float64) / us ** 2
+    return 0.5 * np.sum(d * d, axis=-1) * us[:, 0] ** power, d * us ** power / B * gs
+
+
+@pytest.mark.parametrize('B,H,W', [(5, 64, 16), (1, 9, 7), (3, 33, 5)])          # n = 2048, 126, 330 elements per sample
+@pytest.mark.parametrize('grad_scale', [0.0, 0.25])
+@pytest.mark.parametrize('power', [2.0, 1.5, 0.0])
+def test_dsm_loss_paths(gpu, power, grad_scale, B, H, W):
+    """``anneal_power`` through the sigma^2 shortcut and through powf, ``grad_scale`` (0 reads as 1), sample sizes that are no
+    multiple of the 256 threads, one sample; and ``aux`` = NULL (forward-only plans): the same loss bit for bit."""
+    torch, _lib = gpu
+    from score_based_channels_amd import plan as P
+    rng = np.random.default_rng(int(power * 10) + B)
+    n = H * W * 2
+    sigmas = np.exp(np.linspace(np.log(39.15), np.log(0.0004), 50)).astype(F32)
+    labels = np.array([49, 0, 17, 30, 5][:B], np.int64)
+    us = sigmas[labels]
+    noise = (rng.standard_normal((B, n)).astype(F32) * us[:, None]).astype(F32)
+    s = (rng.standard_normal((B, n)) / us[:, None]).astype(F32)
+    ref_loss, ref_ds = _dsm_reference(s, noise, us, power, B, grad_scale if grad_scale else 1.0)
+    dsig, dlab, ds_, dnz = _dev(torch, sigmas), _dev(torch, labels), _dev(torch, s), _dev(torch, noise)
+    ext = _lib.sbc_dsm(sigmas=_p(dsig), labels=_p(dlab), anneal_power=power, grad_scale=grad_scale)
+    loss = torch.full((B,), float('nan'), dtype=torch.float32, device='cuda')
+    dsc = torch.full((B, n), float('nan'), dtype=torch.float32, device='cuda')
+    op = _lib.sbc_op(kind=P.DSM_LOSS, B=B, H=H, W=W, cin=2, in_=_p(ds_), grad=_p(dnz), out=_p(loss), aux=_p(dsc),
+                     ext=C.cast(C.pointer(ext), C.c_void_p))
+    _launch(gpu, op)
+    assert np.max(np.abs(loss.cpu().numpy() / ref_loss - 1)) < 1e-5
+    assert rel_err(dsc.cpu().numpy(), ref_ds) < 1e-5
+    for b in range(B):                                  # per sample: a small-sigma row must not hide behind a large one
+        assert rel_err(dsc[b].cpu().numpy(), ref_ds[b]) < 1e-5, b
+    loss2 = torch.full((B,), float('nan'), dtype=torch.float32, device='cuda')
+    op2 = _lib.sbc_op(kind=P.DSM_LOSS, B=B, H=H, W=W, cin=2, in_=_p(ds_), grad=_p(dnz), out=_p(loss2), aux=None,
+                      ext=C.cast(C.pointer(ext), C.c_void_p))
+    _launch(gpu, op2)
+    assert torch.equal(loss, loss2)
+
+
+def test_dsm_perturb_philox_keying(gpu):
+    """The draws of sample b depend on (seed, sample_id[b], offset + *step) only: permuting ``sample_id`` permutes the rows bit
+    for bit, NULL reads as arange(B), offset and step add, another seed gives other draws."""
+    torch, _lib = gpu
+    from score_based_channels_amd import plan as P
+    B, H, W = 4, 16, 8
+    n = H * W * 2
+    x = np.zeros((B, n), F32)
+    sigmas = np.array([1.0], F32)
+    dx, dsig, dlab = _dev(torch, x), _dev(torch, sigmas), _dev(torch, np.zeros(B, np.int64))
+
+    def draw(seed, ids, offset, step):
+        did = _dev(torch, np.asarray(ids, np.int64)) if ids is not None else None
+        dstep = _dev(torch, np.array([step], np.int32)) if step is not None else None
+        ext = _lib.sbc_dsm(sigmas=_p(dsig), labels=_p(dlab), sample_id=_p(did), seed=seed, offset=offset, step=_p(dstep),
+                           anneal_power=2.0)
+        pert = torch.full((B, n), float('nan'), dtype=torch.float32, device='cuda')
+        noise = torch.full((B, n), float('nan'), dtype=torch.float32, device='cuda')
+        _launch(gpu, _lib.sbc_op(kind=P.DSM_PERTURB, B=B, H=H, W=W, cin=2, in_=_p(dx), out=_p(pert), aux=_p(noise),
+                                 ext=C.cast(C.pointer(ext), C.c_void_p)))
+        assert torch.equal(pert, noise)                 # x = 0, sigma = 1
+        return noise.cpu().numpy()
+
+    ids = np.array([5, 2, 9, 0])
+    base = draw(7, ids, 3, 0)
+    assert np.isfinite(base).all() and len({base[b].tobytes() for b in range(B)}) == B
+    perm = np.array([2, 0, 3, 1])
+    assert np.array_equal(draw(7, ids[perm], 3, 0), base[perm])
+    assert np.array_equal(draw(7, None, 3, 0), draw(7, np.arange(B), 3, 0))
+    assert np.array_equal(draw(7, np.arange(B), 3, 0)[0], base[3])          # stream 0, wherever it sits in the batch
+    assert np.array_equal(draw(7, ids, 1, 2), base) and np.array_equal(draw(7, ids, 3, None), base)
+    assert not np.array_equal(draw(7, ids, 3, 1), base)
+    other = draw(8, ids, 3, 0)
+    assert np.mean(other == base) < 0.01
+
+
+@pytest.mark.parametrize('n', [1, 255, 4099])
+@pytest.mark.parametrize('t0,ema_mu', [(999, 0.999), (99999, 0.999), (999, -1.0)])
+def test_adam_ema_far_from_step_zero(gpu, t0, ema_mu, n):
+    """One step from a preset counter and moments, against the formula in float64 with python-float bias corrections (1 - 0.999^t
+    is 0.63 at t = 1000 and 1 - 4e-44 at 100 000); ``ema_mu`` < 0 leaves the shadow row alone; sizes below one workgroup."""
+    torch, _lib = gpu
+    from score_based_channels_amd import plan as P
+    rng = np.random.default_rng(t0 + n)
+    lr, b1, b2, eps = 1e-4, 0.9, 0.999, 1e-3
+    p0 = rng.standard_normal(n).astype(F32)
+    g = (rng.standard_normal(n) * 10.0 ** rng.uniform(-4, 1, n)).astype(F32)
+    m0 = (0.5 * g + 0.1 * rng.standard_normal(n)).astype(F32)
+    v0 = (g.astype(np.float64) ** 2 * rng.uniform(0.5, 2, n)).astype(F32)
+    sh0 = rng.standard_normal(n).astype(F32)
+    t = t0 + 1
+    m = m0.astype(np.float64) + (g.astype(np.float64) - m0) * (1 - b1)
+    v = v0.astype(np.float64) * b2 + (1 - b2) * g.astype(np.float64) ** 2
+    p = p0 - (lr / (1 - b1 ** t)) * (m / (np.sqrt(v) / np.sqrt(1 - b2 ** t) + eps))
+    dp, dg = _dev(torch, p0), _dev(torch, g)
+    state = _dev(torch, np.stack([m0, v0, sh0]))
+    step = _dev(torch, np.array([t0], np.int32))
+    ext = _lib.sbc_adam(n=n, lr=lr, beta1=b1, beta2=b2, eps=eps, ema_mu=ema_mu, step=_p(step))
+    _launch(gpu, _lib.sbc_op(kind=P.ADAM_EMA, in_=_p(dg), out=_p(dp), aux=_p(state), ext=C.cast(C.pointer(ext), C.c_void_p)))
+    assert int(step.item()) == t0                       # the counter belongs to SBC_OP_STEP_INC
+    assert np.max(np.abs(dp.cpu().numpy() - p)) < 5e-7
+    assert rel_err(state[0].cpu().numpy(), m) < 1e-6 and rel_err(state[1].cpu().numpy(), v) < 1e-6
+    if ema_mu < 0:
+        assert np.array_equal(state[2].cpu().numpy(), sh0)
+    else:
+        assert np.max(np.abs(state[2].cpu().numpy() - ((1 - ema_mu) * p + ema_mu * sh0.astype(np.float64)))) < 1e-6
+
+
+@pytest.mark.parametrize('elu', [False, True])
+@pytest.mark.parametrize('C_,B,H,W,flat', [(32, 2, 8, 2, False), (128, 3, 16, 1, False), (32, 2, 3, 3, False), (128, 2, 16, 4, False),
+                                           (32, 1, 16, 4, True), (128, 2, 8, 2, True)])
+def test_maxpool5_backward_with_exact_ties(gpu, C_, B, H, W, flat, elu):
+    """Inputs quantised to multiples of 0.5 (most 5 x 5 windows hold their maximum several times) and an all-equal image: the
+    gradient goes to the FIRST maximum in row-major order, as float64 ``max_pool2d`` autograd on the CPU does it.  Images smaller
+    than the window in one or both directions."""
+    torch, _lib = gpu
+    from score_based_channels_amd import plan as P
+    rng = np.random.default_rng(C_ + H + W)
+    x = (np.full((B, H, W, C_), -0.5) if flat else np.round(rng.standard_normal((B, H, W, C_)) * 2) / 2).astype(F32)
+    g = rng.standard_normal(x.shape).astype(F32)
+    xt = _nchw(torch, x)
+    y = torch.nn.functional.max_pool2d(torch.nn.functional.elu(xt) if elu else xt, 5, 1, 2)
+    y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
+    ref = _nhwc(xt.grad)
+    assert flat or np.mean(ref == 0) > 0.5              # ties and losers: most elements receive nothing
+    dx, dg = _dev(torch, x), _dev(torch, g)
+    do = torch.full(x.shape, float('nan'), dtype=torch.float32, device='cuda')
+    aux = torch.empty(x.size, dtype=torch.uint8, device='cuda')
+    op = _lib.sbc_op(kind=P.MAXPOOL5_BWD, flags=P.PRO_ELU if elu else 0, B=B, H=H, W=W, cin=C_, in_=_p(dx), grad=_p(dg),
+                     out=_p(do), aux=_p(aux))
+    _launch(gpu, op)
+    got = do.cpu().numpy()
+    assert np.array_equal(got == 0, ref == 0)           # the same elements win
+    assert rel_err(got, ref) < 1e-6
+
+
+SMALL_CONV_SHAPES = [(2, 256, 64, 4), (3, 16, 64, 4), (5, 8, 8, 8), (2, 24, 16, 12), (1, 128, 8, 32)]     # B, H, W, rows per workgroup
+
+
+def test_small_conv_shapes_reach_the_row_counts_they_are_meant_to():
+    """Restatement of small_rows() of csrc/train_conv.hip (KEEP IN STEP): whole rows of at most 256 pixels that divide H."""
+    for B, H, W, rows in SMALL_CONV_SHAPES + [(3, 64, 16, 16)]:
+        r = min(max(256 // W, 1), H)
+        while H % r:
+            r -= 1
+        assert r == rows, (H, W, r)
+
+
+@pytest.mark.parametrize('B,H,W,rows', SMALL_CONV_SHAPES)
+def test_begin_conv_backward_at_other_images(gpu, B, H, W, rows):
+    """begin_conv's weight and bias gradients at images whose workgroups own 4, 8, 12 and 32 rows (64 x 16 gives 16 only)."""
+    torch, _lib = gpu
+    from score_based_channels_amd import plan as P
+    rng = np.random.default_rng(H + W)
+    x = rng.standard_normal((B, H, W, 2)).astype(F32)
+    g = rng.standard_normal((B, H, W, 32)).astype(F32)
+    wt = torch.zeros(32, 2, 3, 3, dtype=torch.float64, requires_grad=True)
+    bt = torch.zeros(32, dtype=torch.float64, requires_grad=True)
+    y = torch.nn.functional.conv2d(2 * torch.from_numpy(x.transpose(0, 3, 1, 2).copy()).double() - 1, wt, bt, padding=1)
+    y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
+    dx, dg = _dev(torch, x), _dev(torch, g)
+    n_scr = int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, 2, 32, 3))
+    assert n_scr == 16 + B * (H // rows) * (9 * 2 * 32 + 32)
+    aux = torch.zeros(n_scr, dtype=torch.float32, device='cuda')
+    gw = torch.full((32, 2, 3, 3), float('nan'), dtype=torch.float32, device='cuda')
+    gb = torch.full((32,), float('nan'), dtype=torch.float32, device='cuda')
+    op = _lib.sbc_op(kind=P.BEGIN_CONV_BWD, B=B, H=H, W=W, cin=2, cout=32, ksize=3, dil=1, in_=_p(dx), grad=_p(dg),
+                     aux=_p(aux), wgrad=_p(gw), bgrad=_p(gb))
+    _launch(gpu, op)
+    assert rel_err(gw.cpu().numpy(), wt.grad.numpy()) < TOL
+    assert rel_err(gb.cpu().numpy(), bt.grad.numpy()) < TOL
+
+
+@pytest.mark.parametrize('source', ['labels', 'sigma_of_step'])
+@pytest.mark.parametrize('B,H,W,rows', SMALL_CONV_SHAPES)
+def test_end_conv_backward_at_other_images_and_noise_sources(gpu, B, H, W, rows, source):
+    """normalizer -> ELU -> end_conv -> / sigma at the same images; sigma from ``sigmas[labels[b]]`` or, with ``labels`` = NULL,
+    from ``sigma_of_step[*step]`` (one level for the whole batch, as inside a Langevin plan)."""
+    torch, _lib = gpu
+    from score_based_channels_amd import plan as P
+    rng = np.random.default_rng(H * 3 + W)
+    Cc = 32
+    x = rng.standard_normal((B, H, W, Cc)).astype(F32)
+    agb = np.stack([1 + 0.1 * rng.standard_normal(Cc), 1 + 0.1 * rng.standard_normal(Cc), 0.1 * rng.standard_normal(Cc)]).astype(F32)
+    w = (rng.standard_normal((2, Cc, 3, 3)) / 17).astype(F32)
+    g = rng.standard_normal((B, H, W, 2)).astype(F32)
+    sigmas = np.array([3.0, 0.7, 0.05, 11.0, 0.002], F32)
+    labels = np.array([2, 0, 4, 1, 3][:B], np.int64)
+    used = sigmas[labels] if source == 'labels' else np.full(B, sigmas[2], F32)
+    a = torch.nn.functional.elu(_inorm_plus(torch, torch.from_numpy(x.transpose(0, 3, 1, 2).copy()).double(),
+                                            *[torch.from_numpy(agb[i]).double() for i in range(3)])).requires_grad_(True)
+    wt = torch.from_numpy(w).double().requires_grad_(True)
+    bt = torch.zeros(2, dtype=torch.float64, requires_grad=True)
+    y = torch.nn.functional.conv2d(a, wt, bt, padding=1) / torch.from_numpy(used).double()[:, None, None, None]
+    y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
+    dx, dagb, dwt, dg = _dev(torch, x), _dev(torch, agb), _dev(torch, w), _dev(torch, g)
+    dsig, dlab, dstep = _dev(torch, sigmas), _dev(torch, labels), _dev(torch, np.array([2], np.int32))
+    st = _forward_stats(gpu, dx, dagb)
+    if source == 'labels':
+        ext = _lib.sbc_endconv(sigmas=_p(dsig), labels=_p(dlab))
+    else:
+        ext = _lib.sbc_endconv(sigma_of_step=_p(dsig), step=_p(dstep))
+    aux = torch.zeros(int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, Cc, 2, 3)), dtype=torch.float32, device='cuda')
+    out = torch.full((B, H, W, Cc), float('nan'), dtype=torch.float32, device='cuda')
+    gw = torch.full((2, Cc, 3, 3), float('nan'), dtype=torch.float32, device='cuda')
+    gb = torch.full((2,), float('nan'), dtype=torch.float32, device='cuda')
+    op = _lib.sbc_op(kind=P.END_CONV_BWD, B=B, H=H, W=W, cin=Cc, cout=2, ksize=3, dil=1, in_=_p(dx), stats=_p(st),
+                     weight=_p(dwt), grad=_p(dg), out=_p(out), aux=_p(aux), wgrad=_p(gw), bgrad=_p(gb),
+                     ext=C.cast(C.pointer(ext), C.c_void_p))
+    _launch(gpu, op)
+    ref = _nhwc(a.grad)
+    for b in range(B):                                  # per sample: 1 / sigma spans 5000x within the batch
+        assert rel_err(out[b].cpu().numpy(), ref[b]) < TOL, b
+    assert rel_err(gw.cpu().numpy(), wt.grad.numpy()) < TOL
+    assert rel_err(gb.cpu().numpy(), bt.grad.numpy()) < TOL
+
+
+@pytest.mark.parametrize('C_,B,H,W,offset', [(32, 1, 64, 16, 0.0), (64, 1, 16, 1, 0.0), (128, 3, 16, 1, 0.0), (64, 3, 16, 4, 50.0),
+                                             (32, 2, 64, 16, 50.0), (128, 40, 8, 2, 0.0)])
+def test_inorm_backward_edges(gpu, C_, B, H, W, offset):
+    """One sample; 16-pixel planes one pixel wide; planes whose mean is 50 standard deviations from zero (``x - mu`` cancels six
+    bits of every float32 input); 40 samples of 128 channels for the batch sum of the parameter gradients in the last workgroup.
+
+    The offset is +50 or -50 per channel.  With the SAME offset for every channel the input would test something else: the "++"
+    term divides ``mu_c - m`` by the spread of the channel means, and with all means near 50 that difference of two float32
+    numbers is itself only good to ulp(50) / spread = 2e-5 -- a float32 torch evaluation of such an input sits 1.5e-5 ... 2.4e-5
+    from float64 (measured on the CPU), at this file's bound, whatever the kernel does.  With means of both signs the same
+    evaluation sits at 2.5e-6 ... 4.5e-6, below half of the bound, and the cancellation in ``x - mu`` is still there."""
+    torch, _lib = gpu
+    from score_based_channels_amd import plan as P
+    rng = np.random.default_rng(C_ + B + H)
+    sign = np.where(rng.random((1, 1, 1, C_)) < 0.5, -1.0, 1.0)
+    x = (rng.standard_normal((B, H, W, C_)) + (offset * sign + 0.2 * rng.standard_normal((B, 1, 1, C_)))).astype(F32)
+    agb = np.stack([1 + 0.1 * rng.standard_normal(C_), 1 + 0.1 * rng.standard_normal(C_), 0.1 * rng.standard_normal(C_)]).astype(F32)
+    g = rng.standard_normal(x.shape).astype(F32)
+    xt = _nchw(torch, x)
+    pt = [torch.from_numpy(agb[i]).double().requires_grad_(True) for i in range(3)]
+    y = torch.nn.functional.elu(_inorm_plus(torch, xt, *pt))
+    y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
+    ref_dx, ref_dp = _nhwc(xt.grad), np.stack([p.grad.numpy() for p in pt])
+    dx, dagb, dg = _dev(torch, x), _dev(torch, agb), _dev(torch, g)
+    do = torch.full(x.shape, float('nan'), dtype=torch.float32, device='cuda')
+    st = _forward_stats(gpu, dx, dagb)
+    aux = torch.empty(B * 6 * C_, dtype=torch.float32, device='cuda')
+    dp = torch.full((3, C_), float('nan'), dtype=torch.float32, device='cuda')
+    op = _lib.sbc_op(kind=P.INORM_BWD, flags=P.PRO_ELU, B=B, H=H, W=W, cin=C_, in_=_p(dx), stats=_p(st), weight=_p(dagb),
+                     grad=_p(dg), out=_p(do), aux=_p(aux), wgrad=_p(dp))
+    _launch(gpu, op)
+    e_dx, e_dp = rel_err(do.cpu().numpy(), ref_dx), rel_err(dp.cpu().numpy(), ref_dp)
+    print('inorm_bwd C%d B%d %dx%d offset %g: dx %.2e, d(alpha, gamma, beta) %.2e' % (C_, B, H, W, offset, e_dx, e_dp))
+    assert e_dx < TOL
+    assert e_dp < TOL
+
+
+ELEMENTWISE_SHAPES = [(32, 1, 2, 2), (128, 3, 2, 2), (32, 3, 256, 64), (128, 1, 256, 64)]
+
+
+@pytest.mark.parametrize('C_,B,H,W', ELEMENTWISE_SHAPES)
+def test_pool_backward_shapes(gpu, C_, B, H, W):
+    torch, _lib = gpu
+    from score_based_channels_amd import plan as P
+    rng = np.random.default_rng(C_ + H)
+    g = rng.standard_normal((B, H // 2, W // 2, C_)).astype(F32)
+    dg = _dev(torch, g)
+    out = torch.full((B, H, W, C_), float('nan'), dtype=torch.float32, device='cuda')
+    _launch(gpu, _lib.sbc_op(kind=P.POOL_BWD, B=B, H=H, W=W, cin=C_, grad=_p(dg), out=_p(out)))
+    assert np.array_equal(out.cpu().numpy(), (np.repeat(np.repeat(g, 2, axis=1), 2, axis=2) * 0.25).astype(F32))
+
+
+@pytest.mark.parametrize('elu,accum', [(False, True), (True, False), (True, True)])
+@pytest.mark.parametrize('C_,B,H,W', ELEMENTWISE_SHAPES)
+def test_grad_add_shapes(gpu, C_, B, H, W, elu, accum):
+    torch, _lib = gpu
+    from score_based_channels_amd import plan as P
+    rng = np.random.default_rng(C_ + H + B)
+    x = rng.standard_normal((B, H, W, C_)).astype(F32) * 2
+    g = rng.standard_normal(x.shape).astype(F32)
+    o0 = rng.standard_normal(x.shape).astype(F32)
+    ref = g * (np.where(x > 0, 1.0, np.exp(x.astype(np.float64))) if elu else 1.0) + (o0 if accum else 0.0)
+    dx, dg, do = _dev(torch, x), _dev(torch, g), _dev(torch, o0)
+    op = _lib.sbc_op(kind=P.GRAD_ADD, flags=(P.PRO_ELU if elu else 0) | (P.BWD_ACCUM if accum else 0), B=B, H=H, W=W, cin=C_,
+                     in_=_p(dx), grad=_p(dg), out=_p(do))
+    _launch(gpu, op)
+    assert rel_err(do.cpu().numpy(), ref) < 1e-6
+
+
+@pytest.mark.parametrize('C_,B,H,W,uh,uw,accum', [(128, 3, 16, 1, 8, 1, False), (128, 2, 2, 8, 1, 4, True), (32, 2, 64, 16, 8, 2, False),
+                                                   (32, 1, 256, 64, 32, 8, True), (64, 3, 2, 2, 1, 1, False)])
+def test_upsample_backward_degenerate_windows(gpu, C_, B, H, W, uh, uw, accum):
+    """One-pixel-wide and one-pixel-high sources (the scale along that axis is 0 and every fine pixel reads source pixel 0), a
+    ratio of 8, and the largest resize of a 256 x 64 array.  Reference: autograd through the restatement's resize, which forms the
+    source coordinate in float32 as the forward kernel does (torch's float64 ``interpolate`` forms it in float64)."""
+    torch, _lib = gpu
+    import scorenet_autograd as SA
+    from score_based_channels_amd import plan as P
+    rng = np.random.default_rng(H + uh + W)
+    g = rng.standard_normal((B, H, W, C_)).astype(F32)
+    o0 = rng.standard_normal((B, uh, uw, C_)).astype(F32)
+    u = _nchw(torch, o0)
+    y = SA.bilinear_align_corners(u, (H, W))
+    y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
+    ref = _nhwc(u.grad) + (o0 if accum else 0.0)
+    dg, do = _dev(torch, g), _dev(torch, o0)
+    op = _lib.sbc_op(kind=P.UPSAMPLE_BWD, flags=P.BWD_ACCUM if accum else 0, B=B, H=H, W=W, cin=C_, up_h=uh, up_w=uw,
+                     grad=_p(dg), out=_p(do))
+    _launch(gpu, op)
+    assert rel_err(do.cpu().numpy(), ref) < 2e-6
+
+
+def test_conv_weight_gradient_refuses_an_image_it_cannot_tile(gpu):
+    """12 x 4 = 48 pixels is neither a multiple nor a divisor of the 64-pixel tile: the launch returns the error status with its
+    message and writes nothing."""
+    torch, _lib = gpu
+    from score_based_channels_amd import plan as P
+    B, H, W, c = 2, 12, 4, 64
+    dx = torch.zeros(B, H, W, c, dtype=torch.float32, device='cuda')
+    dg = torch.zeros(B, H, W, c, dtype=torch.float32, device='cuda')
+    aux = torch.zeros(int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, c, c, 3)), dtype=torch.float32, device='cuda')
+    dw = torch.full((c, c, 3, 3), float('nan'), dtype=torch.float32, device='cuda')
+    db = torch.full((c,), float('nan'), dtype=torch.float32, device='cuda')
+    op = _lib.sbc_op(kind=P.CONV_WGRAD, flags=P.PRO_ELU, B=B, H=H, W=W, cin=c, cout=c, ksize=3, dil=1, in_=_p(dx), grad=_p(dg),
+                     aux=_p(aux), wgrad=_p(dw), bgrad=_p(db))
+    rc = _lib.lib().sbc_op_launch(C.byref(op), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    assert rc != 0 and 'does not tile' in _lib.lib().sbc_last_error().decode()
+    with pytest.raises(_lib.SbcError, match='12x4'):
+        _lib.check(rc)
+    assert bool(torch.isnan(dw).all()) and bool(torch.isnan(db).all()) and float(aux.abs().max()) == 0.0
