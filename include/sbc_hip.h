@@ -22,6 +22,11 @@
  *     the calling thread's last failure.  Nothing throws across the ABI.  Launches are asynchronous on the
  *     given stream (pass torch.cuda.current_stream().cuda_stream); no hidden device synchronisation
  *     except in the functions documented as synchronising.
+ *
+ * Beside the plan interface the library carries the other estimators of the paper's Fig. 5c, each a self-contained group of calls
+ * with its own section below: the lifted-DFT l1 solver and regularised least squares (sbc_l1_lifted_run, sbc_ls_regularized), Learned
+ * D-AMP (sbc_ldamp_*) and the WGAN latent optimisation (sbc_wgan_*: generator forward, backward and Adam on the latents).  The two
+ * network baselines keep their activations planar, [N][C][H][W] float32, in a workspace the caller owns.
  */
 #ifndef SBC_HIP_H
 #define SBC_HIP_H
@@ -642,6 +647,62 @@ int sbc_ldamp_denoise(sbc_ldamp* handle, int32_t net, const float* r, float* out
 int sbc_ldamp_run(sbc_ldamp* handle, const sbc_ldamp_run_desc* desc, void* stream);
 int sbc_ldamp_stage(int32_t stage, int32_t n_images, int64_t* offset, int32_t* channels, int32_t* height, int32_t* width);
 int sbc_debug_ldamp_directions(uint64_t seed, int64_t sample, int32_t unroll, float* out);
+
+/* --- WGAN latent optimisation (the WGAN baseline of Fig. 5c) ---------------------------------------------------------------------
+ * src/score_based_channels/test_wgan.py:129-176 with the generator aux_gan.py:58-112 (DCGAN_G_Ours) in eval mode, isize = [16, 64]
+ * (Nr, Nt), nz = 60, nc = 2, ngf = 128, L = 2 + n_extra hidden layers, n_extra = 0 .. 4 read from the tensor names (csrc/wgan.hip):
+ *     dense Linear(60 -> 8192) viewed [128][4][16];  layers 1, 2: nearest x 2, Conv 5 x 5 128 -> 128 + bias, BatchNorm (running
+ *     statistics, eps 1e-5), ReLU;  layers 3 .. L: Conv 3 x 3 128 -> 128 (no bias), BatchNorm, ReLU;  out: Conv 5 x 5 128 -> 2 + bias.
+ * One step of sample b, with G = gen[0] + i gen[1] [16][64]:  meas = ||G P - Y||_F^2, reg = ||z||^2, loss = s_b (meas + lambda_b reg),
+ * g = d loss / d z, then torch.optim.Adam's defaults (betas 0.9 / 0.999, eps 1e-8, bias correction) on z with step size lr_b.  The logs
+ * of step k are taken at z_k, before the update.  Samples are independent: lambda, lr and s are per-sample arrays (the reference's
+ * torch.mean over its batch is s_b = 1 / kept_samples), so all (lambda, lr, SNR) cells of one pilot count run as one batch.
+ * Exact fp32 arithmetic, the 128 -> 128 convolutions on the fp32 matrix cores, fixed summation orders, no atomics: a sample's result does
+ * not depend on its position in the batch, on B or on repetition, bit for bit.  Complex data are interleaved float32 (re, im); all
+ * data pointers are DEVICE pointers except where noted.
+ *
+ *   sbc_wgan_create            copies the generator from HOST float tensors named as in the reference's state_dict ("dense.dense_input.*",
+ *                              "conv.conv1.*", "conv.bn1.{weight,bias,running_mean,running_var}", .., "conv.extra_conv<i>.weight",
+ *                              "conv.extra_bn<i>.*", "conv.conv_out.*": 16 + 5 n_extra tensors, torch layouts, num_batches_tracked left
+ *                              out; every name and element count is checked) to the current device and packs the filters for both
+ *                              directions.  Synchronises (hipMemcpy).  The handle is bound to that device.
+ *   sbc_wgan_workspace_floats  float32 elements of `workspace` a call with B samples needs; -1 on a bad argument.
+ *   sbc_wgan_generate          out [B][2][16][64] = G(z [B][60]); L + 2 launches + 1 copy, asynchronous on `stream`.
+ *   sbc_wgan_run               n_steps steps for B samples, 2 L + 4 launches per step, asynchronous on `stream`.  Every argument is checked
+ *                              before anything is launched; B = 0 or n_steps = 0 launches nothing.
+ *   sbc_wgan_stage             where a stage of the last call lies in its workspace: `offset` floats from the start, as
+ *                              [B][channels][height][width].  Stages: k = 0 .. L the activations (0: the dense output [128][4][16], k >= 1:
+ *                              layer k after its ReLU); 16 gen [2][16][64]; 17 dG = d loss / d gen; 32 + k, k = 0 .. L, d loss / d
+ *                              (activation k); 48 + k, k = 1 .. L, the ReLU sign mask of layer k as 32-bit words [128][height][W / 32]
+ *                              (bit j of word q: pixel x = 32 q + j is positive).  Stages 17 and 32 + k hold the last step of a run; a
+ *                              generate call writes 0 .. L, 16 and the masks.  No stage shares memory with another. */
+typedef struct sbc_wgan sbc_wgan;
+typedef struct sbc_wgan_run_desc {
+    const float* Y;            /* [B][16][Np] complex measurements (val_Y)                                                       */
+    const float* P;            /* [B][64][Np] complex pilots (val_P)                                                             */
+    const float* H;            /* [B][16][64] complex channels for oracle_log, or NULL                                           */
+    float* z;                  /* [B][60] latents, in and out                                                                    */
+    float* m;                  /* [B][60] Adam's exp_avg, in and out (zeros before the first step)                               */
+    float* v;                  /* [B][60] Adam's exp_avg_sq, in and out                                                          */
+    const float* lr;           /* [B]                                                                                            */
+    const float* l2_lam;       /* [B]                                                                                            */
+    const float* loss_scale;   /* [B] s_b                                                                                        */
+    float* oracle_log;         /* [n_steps][B] ||G - H||^2 / ||H||^2, or NULL (needs H)                                          */
+    float* meas_log;           /* [n_steps][B], or NULL                                                                          */
+    float* reg_log;            /* [n_steps][B], or NULL                                                                          */
+    float* z_log;              /* [n_steps][B][60] z before each update, or NULL                                                 */
+    float* g_log;              /* [n_steps][B][60] d loss / d z of each step, or NULL                                            */
+    float* workspace;          /* sbc_wgan_workspace_floats(handle, B) floats                                                    */
+    int32_t B, Np;             /* 1 <= Np <= 64                                                                                  */
+    int32_t first_step;        /* Adam's t of the first step (1 for a fresh run; continue a run with 1 + the steps already taken) */
+    int32_t n_steps;
+} sbc_wgan_run_desc;
+int sbc_wgan_create(const sbc_tensor_ref* tensors, int32_t n_tensors, sbc_wgan** out);
+void sbc_wgan_destroy(sbc_wgan* handle);
+int64_t sbc_wgan_workspace_floats(const sbc_wgan* handle, int32_t B);
+int sbc_wgan_generate(sbc_wgan* handle, const float* z, float* out, int32_t B, float* workspace, void* stream);
+int sbc_wgan_run(sbc_wgan* handle, const sbc_wgan_run_desc* desc, void* stream);
+int sbc_wgan_stage(const sbc_wgan* handle, int32_t stage, int32_t B, int64_t* offset, int32_t* channels, int32_t* height, int32_t* width);
 
 /* ---- Environment variables -------------------------------------------------------------------------------------------------
  * Everything the library (csrc/) and the Python host (score_based_channels_amd/) read from the environment, in ONE place.  None of them

@@ -20,7 +20,8 @@ EXPORTS = ('sbc_abi_version', 'sbc_set_persistent_cus', 'sbc_last_error', 'sbc_d
            'sbc_score_create', 'sbc_score_buffers', 'sbc_score_ops', 'sbc_score_level_source', 'sbc_score_forward',
            'sbc_score_destroy', 'sbc_wgrad_scratch_floats', 'sbc_l1_lifted_run', 'sbc_ls_regularized',
            'sbc_ldamp_create', 'sbc_ldamp_destroy', 'sbc_ldamp_workspace_floats', 'sbc_ldamp_denoise', 'sbc_ldamp_run', 'sbc_ldamp_stage',
-           'sbc_debug_ldamp_directions')
+           'sbc_debug_ldamp_directions',
+           'sbc_wgan_create', 'sbc_wgan_destroy', 'sbc_wgan_workspace_floats', 'sbc_wgan_generate', 'sbc_wgan_run', 'sbc_wgan_stage')
 
 
 class SbcError(RuntimeError):
@@ -107,6 +108,14 @@ class sbc_ldamp_run_desc(C.Structure):
                 ('B', C.c_int32), ('Np', C.c_int32), ('Nt', C.c_int32), ('Nr', C.c_int32), ('num_unrolls', C.c_int32)]
 
 
+# WGAN latent optimisation (wgan.py)
+class sbc_wgan_run_desc(C.Structure):
+    _fields_ = [('Y', C.c_void_p), ('P', C.c_void_p), ('H', C.c_void_p), ('z', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p),
+                ('lr', C.c_void_p), ('l2_lam', C.c_void_p), ('loss_scale', C.c_void_p), ('oracle_log', C.c_void_p),
+                ('meas_log', C.c_void_p), ('reg_log', C.c_void_p), ('z_log', C.c_void_p), ('g_log', C.c_void_p), ('workspace', C.c_void_p),
+                ('B', C.c_int32), ('Np', C.c_int32), ('first_step', C.c_int32), ('n_steps', C.c_int32)]
+
+
 _lib = None
 
 
@@ -164,6 +173,15 @@ def lib():
     h.sbc_ldamp_run.argtypes = [C.c_void_p, C.POINTER(sbc_ldamp_run_desc), C.c_void_p]
     h.sbc_ldamp_stage.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     h.sbc_debug_ldamp_directions.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_void_p]
+    h.sbc_wgan_create.argtypes = [C.POINTER(sbc_tensor_ref), C.c_int32, C.POINTER(C.c_void_p)]
+    h.sbc_wgan_destroy.argtypes = [C.c_void_p]
+    h.sbc_wgan_destroy.restype = None
+    h.sbc_wgan_workspace_floats.argtypes = [C.c_void_p, C.c_int32]
+    h.sbc_wgan_workspace_floats.restype = C.c_int64
+    h.sbc_wgan_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    h.sbc_wgan_run.argtypes = [C.c_void_p, C.POINTER(sbc_wgan_run_desc), C.c_void_p]
+    h.sbc_wgan_stage.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32)]
     if h.sbc_abi_version() != ABI_VERSION:
         raise SbcError('libsbc_hip.so ABI %d != expected %d' % (h.sbc_abi_version(), ABI_VERSION))
     _lib = h

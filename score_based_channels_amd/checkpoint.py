@@ -40,8 +40,9 @@ def _to_config(node):
     return node
 
 
-def load_checkpoint(path, map_location='cpu'):
-    """-> dict with ``model_state`` (name -> tensor) and ``config`` (``Config``); other keys passed through."""
+def load_checkpoint(path, map_location='cpu', required=('model_state', 'config')):
+    """-> dict with ``model_state`` (name -> tensor) and ``config`` (``Config``); other keys passed through.  ``required``: the keys
+    the file must hold (the WGAN checkpoints of ``train_wgan.py`` hold ``gen_state`` instead of ``model_state``)."""
     import torch
     had = sys.modules.get('dotmap')
     shim = types.ModuleType('dotmap')
@@ -56,8 +57,9 @@ def load_checkpoint(path, map_location='cpu'):
         else:
             del sys.modules['dotmap']
         _DotMapShim.__module__, _DotMapShim.__qualname__ = __name__, '_DotMapShim'
-    if 'model_state' not in contents or 'config' not in contents:
-        raise KeyError("%s is not a score-model checkpoint (needs 'model_state' and 'config')" % path)
+    if any(k not in contents for k in required):
+        kind = 'a score-model' if 'model_state' in required else 'the expected kind of'
+        raise KeyError("%s is not %s checkpoint (needs %s)" % (path, kind, ' and '.join(repr(k) for k in required)))
     contents['config'] = _to_config(contents['config'])
     return contents
 
