@@ -198,11 +198,14 @@ class LDAMP:
         if not 0 <= int(net) < self.max_unrolls:
             raise ValueError('net must be in [0, %d) (got %r)' % (self.max_unrolls, net))
         dev = self._torch_device()
-        r = r.to(dev).resolve_conj().contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):           # whatever torch has to copy or convert is ordered on the same stream
+            r = r.to(dev).resolve_conj().contiguous()
         B = r.shape[0]
         out = torch.empty_like(r)
+        if B == 0:                                       # an empty tensor has no address to hand to the library
+            return out
         with torch.cuda.device(dev):
-            s = stream if stream is not None else torch.cuda.current_stream(dev)
             ws = self._workspace(B, 0, dev)
             _lib.check(_lib.lib().sbc_ldamp_denoise(self._h, int(net), C.c_void_p(r.data_ptr()), C.c_void_p(out.data_ptr()), B,
                                                     C.c_void_p(ws.data_ptr()), C.c_void_p(s.cuda_stream)))
@@ -242,12 +245,14 @@ class LDAMP:
         if H is not None and (not isinstance(H, torch.Tensor) or H.dtype != torch.complex64 or tuple(H.shape) != (B, NT, NR)):
             raise ValueError('H must be a complex64 tensor [%d, %d, %d]' % (B, NT, NR))
         dev = self._torch_device()
-        Y, P = Y.to(dev).resolve_conj().contiguous(), P.to(dev).resolve_conj().contiguous()
-        eig = eig.to(dev, torch.float32).contiguous()
-        if directions is not None:
-            directions = directions.to(dev, torch.float32).contiguous()
-        if H is not None:
-            H = H.to(dev).resolve_conj().contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):           # whatever torch has to copy or convert is ordered on the same stream
+            Y, P = Y.to(dev).resolve_conj().contiguous(), P.to(dev).resolve_conj().contiguous()
+            eig = eig.to(dev, torch.float32).contiguous()
+            if directions is not None:
+                directions = directions.to(dev, torch.float32).contiguous()
+            if H is not None:
+                H = H.to(dev).resolve_conj().contiguous()
         H_hat = torch.empty((B, NT, NR), dtype=torch.complex64, device=dev)
         logs = {}
         if return_logs:
@@ -256,9 +261,12 @@ class LDAMP:
                     'div': torch.empty((U, B), dtype=torch.float32, device=dev),
                     'eps': torch.empty((U, B), dtype=torch.float32, device=dev)}
         nmse = torch.empty((B,), dtype=torch.float32, device=dev) if H is not None else None
+        if nmse is not None:
+            logs['nmse'] = nmse
+        if B == 0:                                       # an empty tensor has no address to hand to the library
+            return (H_hat, logs) if (return_logs or H is not None) else H_hat
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None           # noqa: E731
         with torch.cuda.device(dev):
-            s = stream if stream is not None else torch.cuda.current_stream(dev)
             ws = self._workspace(B, U, dev)
             d = _lib.sbc_ldamp_run_desc(Y_herm=ptr(Y), P_herm=ptr(P), eig1=ptr(eig), directions=ptr(directions), Htrue=ptr(H),
                                         H_hat=ptr(H_hat), nmse=ptr(nmse), h_log=ptr(logs.get('h')), z_log=ptr(logs.get('z')),
@@ -269,8 +277,6 @@ class LDAMP:
                 if t is not None:
                     t.record_stream(s)
         self.last_workspace = (ws, 2 * B)
-        if nmse is not None:
-            logs['nmse'] = nmse
         return (H_hat, logs) if (return_logs or H is not None) else H_hat
 
     def close(self):

@@ -238,13 +238,14 @@ class DCGAN_G_Ours:
         import torch
         self._need_weights()
         dev = self._torch_device()
-        z = self._latents(z, dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(s):           # whatever torch has to copy or convert is ordered on the same stream
+            z = self._latents(z, dev)
         B = z.shape[0]
         out = torch.empty((B, NC, NR, NT), dtype=torch.float32, device=dev)
         if B == 0:
             return out
         with torch.cuda.device(dev):
-            s = stream if stream is not None else torch.cuda.current_stream(dev)
             ws = self._workspace(B, dev)
             _lib.check(_lib.lib().sbc_wgan_generate(self._h, C.c_void_p(z.data_ptr()), C.c_void_p(out.data_ptr()), B,
                                                     C.c_void_p(ws.data_ptr()), C.c_void_p(s.cuda_stream)))
@@ -304,17 +305,20 @@ class LatentOptimizer:
         B, Np = check_run_args(tuple(np.shape(z0)), tuple(Y.shape), tuple(P.shape), steps, None if H is None else tuple(H.shape), first)
         steps = int(steps)
         dev = G._torch_device()
-        z = G._latents(z0, dev).clone()
-        Y, P = Y.to(dev).resolve_conj().contiguous(), P.to(dev).resolve_conj().contiguous()
-        H = H.to(dev).resolve_conj().contiguous() if H is not None else None
-        arr = {k: torch.from_numpy(per_sample(v, B, k)).to(dev)
-               for k, v in (('lr', lr), ('l2_lam', l2_lam), ('loss_scale', 1.0 / max(B, 1) if loss_scale is None else loss_scale))}
-        if state is not None:
-            m, v = (state[k].detach().to(dev, torch.float32).clone().contiguous() for k in ('m', 'v'))
-            if tuple(m.shape) != (B, NZ) or tuple(v.shape) != (B, NZ):
-                raise ValueError('state m and v must be [%d, %d]' % (B, NZ))
-        else:
-            m, v = torch.zeros_like(z), torch.zeros_like(z)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        # the copies, conversions and zero fills torch launches here are ordered on the stream the kernels run on
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            z = G._latents(z0, dev).clone()
+            Y, P = Y.to(dev).resolve_conj().contiguous(), P.to(dev).resolve_conj().contiguous()
+            H = H.to(dev).resolve_conj().contiguous() if H is not None else None
+            arr = {k: torch.from_numpy(per_sample(v, B, k)).to(dev)
+                   for k, v in (('lr', lr), ('l2_lam', l2_lam), ('loss_scale', 1.0 / max(B, 1) if loss_scale is None else loss_scale))}
+            if state is not None:
+                m, v = (state[k].detach().to(dev, torch.float32).clone().contiguous() for k in ('m', 'v'))
+                if tuple(m.shape) != (B, NZ) or tuple(v.shape) != (B, NZ):
+                    raise ValueError('state m and v must be [%d, %d]' % (B, NZ))
+            else:
+                m, v = torch.zeros_like(z), torch.zeros_like(z)
         logs = {}
         if return_logs:
             logs = {'meas': torch.empty((steps, B), dtype=torch.float32, device=dev), 'reg': torch.empty((steps, B), dtype=torch.float32, device=dev)}
@@ -327,7 +331,6 @@ class LatentOptimizer:
         if B == 0 or steps == 0:
             return z, {'m': m, 'v': v, 'step': first - 1 + steps}, logs
         with torch.cuda.device(dev):
-            s = stream if stream is not None else torch.cuda.current_stream(dev)
             ws = G._workspace(B, dev)
             d = _lib.sbc_wgan_run_desc(Y=ptr(Y), P=ptr(P), H=ptr(H), z=ptr(z), m=ptr(m), v=ptr(v), lr=ptr(arr['lr']), l2_lam=ptr(arr['l2_lam']),
                                        loss_scale=ptr(arr['loss_scale']), oracle_log=ptr(logs.get('oracle')), meas_log=ptr(logs.get('meas')),
@@ -337,5 +340,7 @@ class LatentOptimizer:
             for t in (Y, P, H, ws, z, m, v) + tuple(arr.values()) + tuple(logs.values()):
                 if t is not None:
                     t.record_stream(s)
+            for t in (z, m, v):                                       # allocated under `s`, handed to a caller on the current stream
+                t.record_stream(torch.cuda.current_stream(dev))
         G.last_workspace = (ws, B)
         return z, {'m': m, 'v': v, 'step': first - 1 + steps}, logs

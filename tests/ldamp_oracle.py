@@ -120,6 +120,38 @@ def run_oracle(sd, Y, P, eig, directions, num_unrolls, dtype=torch.float64):
     return run(lambda u, x: denoise_planes(sd, u, x, dtype), Y, P, eig, directions, num_unrolls, dtype)
 
 
+# ---- the flipped twin: the same function in another valid summation order ---------------------------------------------------------
+# Every filter flipped in its last two axes, the input flipped, the output flipped back.  Every operation of the net commutes with the
+# flip (the statistics are over whole planes, the 2 x 2 pool and the stride-2 transposed convolution tile even extents), so in exact
+# arithmetic the twin is the identity; in float32 its sums run in another order and it gives different bits.
+def flip(x):
+    return torch.flip(x, (-2, -1))
+
+
+def flip_state_dict(sd):
+    return {k: (v[..., ::-1, ::-1].copy() if np.ndim(v) == 4 else v) for k, v in sd.items()}
+
+
+def twin(layer):
+    """a layer function f(x, ..., w) -> f on flipped tensors, flipped back (every >= 3-D tensor argument is flipped)"""
+    def f(*args):
+        return flip(layer(*[flip(a) if (isinstance(a, torch.Tensor) and a.dim() >= 3 and a.shape[-1] * a.shape[-2] > 1) else a for a in args]))
+    return f
+
+
+def denoise_planes_flipped(fsd, net, x, dtype, stages=None):
+    """``denoise_planes`` through the twin; ``fsd = flip_state_dict(sd)``"""
+    st = {}
+    out = flip(denoise_planes(fsd, net, flip(x).contiguous(), dtype, st))
+    if stages is not None:
+        stages.update({k: (v if k == 'stat' else flip(v)) for k, v in st.items()})
+    return out
+
+
+def run_oracle_flipped(fsd, Y, P, eig, directions, num_unrolls, dtype=torch.float32):
+    return run(lambda u, x: denoise_planes_flipped(fsd, u, x, dtype), Y, P, eig, directions, num_unrolls, dtype)
+
+
 # ---- the error measure of the tests ---------------------------------------------------------------------------------------------
 def normwise(a, ref):
     """per-sample norm-wise relative error, maximum over samples (axis 0 = sample)"""

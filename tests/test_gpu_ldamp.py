@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import ldamp_cases as LC
 import ldamp_oracle as O
 from conftest import load_golden
 from score_based_channels_amd import _lib, ldamp
@@ -68,52 +69,50 @@ def test_one_evaluation(model, weights, net):
     assert_all([check('denoise net %d' % net, got, ref64, ref32)])
 
 
-def test_each_layer_kind(model, weights):
-    """Every launch of one evaluation on its own: the stage's input as the kernel left it in the workspace goes through the oracle's layer in
-    float64 and float32; the kernel's output of that stage is held to the rule.  Kinds: first ConvBlock (x -> d0a -> d0), pooled ConvBlock
-    (-> p0 / p1 / p2: the pool is the producer's epilogue), the 8x2 bottleneck (ba, bb), transposed-conv stages (t0, t1, t2), two-source
-    ConvBlocks (u0a, u1a, u2a), and the 1x1 with unnorm and residual (the output)."""
-    g = O.golden_unet()
-    out = model.denoise(0, dev(g['r'])).cpu().numpy()
+def kernel_stages(model, net, r):
+    """one evaluation on the GPU -> every stage as the kernel left it in the workspace (name -> array), the output planes as 'out'"""
+    out = model.denoise(net, dev(r)).cpu().numpy()
     st = {n: model.stage(n).cpu().numpy() for n in ldamp.STAGES}
-    W = lambda k, dt: torch.from_numpy(weights['update_nets.0.unet.' + k]).to(dt)           # noqa: E731
-    T = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt)                       # noqa: E731
+    st['out'] = np.stack((out.real, out.imag), axis=1)
+    assert np.array_equal(st['r'][..., 0] + 1j * st['r'][..., 1], r)
+    return st
+
+
+def each_layer_kind(model, state_dict, r, net, twin=False):
+    """Every launch of one evaluation on its own: the stage's input as the kernel left it in the workspace goes through the oracle's layer in
+    float64 and float32; the kernel's output of that stage is held to the rule.  Kinds: norm, first ConvBlock (x -> d0a -> d0), pooled
+    ConvBlock (-> p0 / p1 / p2: the pool is the producer's epilogue), the 8x2 bottleneck (ba, bb), transposed-conv stages (t0, t1, t2),
+    two-source ConvBlocks (u0a, u1a, u2a), and the 1x1 with unnorm and residual (the output).  ``twin``: e_ref is the larger of the
+    native and the flipped float32 order (tests/ldamp_cases.py) instead of the native one alone."""
+    st = kernel_stages(model, net, r)
     res = []
-
-    def both(f):
-        with torch.no_grad():
-            return f(torch.float64).numpy(), f(torch.float32).numpy()
-
-    # norm (part of the first launch)
-    r = st['r']
-    planes = np.stack((r[..., 0], r[..., 1]), axis=1)
-    assert np.array_equal(r[..., 0] + 1j * r[..., 1], g['r'])
-    res.append(check('norm', st['x'], *both(lambda dt: O.norm(T(planes, dt))[0])))
-    chain = [('d0a', 'x', 'down_sample_layers.0.layers.0.weight'), ('d0', 'd0a', 'down_sample_layers.0.layers.4.weight'),
-             ('d1a', 'p0', 'down_sample_layers.1.layers.0.weight'), ('d1', 'd1a', 'down_sample_layers.1.layers.4.weight'),
-             ('d2a', 'p1', 'down_sample_layers.2.layers.0.weight'), ('d2', 'd2a', 'down_sample_layers.2.layers.4.weight'),
-             ('ba', 'p2', 'conv.layers.0.weight'), ('bb', 'ba', 'conv.layers.4.weight'),
-             ('u0', 'u0a', 'up_conv.0.layers.4.weight'), ('u1', 'u1a', 'up_conv.1.layers.4.weight'), ('u2', 'u2a', 'up_conv.2.0.layers.4.weight')]
-    for o, i, k in chain:
-        res.append(check('conv half %s -> %s' % (i, o), st[o], *both(lambda dt: O.conv_half(T(st[i], dt), W(k, dt)))))
-    for p, i, k in (('p0', 'd0a', 'down_sample_layers.0.layers.4.weight'), ('p1', 'd1a', 'down_sample_layers.1.layers.4.weight'),
-                    ('p2', 'd2a', 'down_sample_layers.2.layers.4.weight')):
-        res.append(check('pooled conv half %s -> %s' % (i, p), st[p], *both(lambda dt: O.pool(O.conv_half(T(st[i], dt), W(k, dt))))))
-    for t, i, k in (('t0', 'bb', 'up_transpose_conv.0.layers.0.weight'), ('t1', 'u0', 'up_transpose_conv.1.layers.0.weight'),
-                    ('t2', 'u1', 'up_transpose_conv.2.layers.0.weight')):
-        res.append(check('transposed conv %s -> %s' % (i, t), st[t], *both(lambda dt: O.tconv_stage(T(st[i], dt), W(k, dt)))))
-    for o, a, b, k in (('u0a', 't0', 'd2', 'up_conv.0.layers.0.weight'), ('u1a', 't1', 'd1', 'up_conv.1.layers.0.weight'),
-                       ('u2a', 't2', 'd0', 'up_conv.2.0.layers.0.weight')):
-        res.append(check('two-source conv half %s+%s -> %s' % (a, b, o), st[o],
-                         *both(lambda dt: O.conv_half(torch.cat([T(st[a], dt), T(st[b], dt)], dim=1), W(k, dt)))))
-
-    def fin(dt):
-        s = T(st['stat'], dt)
-        mean, std = s[:, [0, 2]][:, :, None, None], s[:, [1, 3]][:, :, None, None]
-        return O.final(T(st['u2'], dt), W('up_conv.2.1.weight', dt), W('up_conv.2.1.bias', dt), mean, std, T(planes, dt))
-    outp = np.stack((out.real, out.imag), axis=1)
-    res.append(check('1x1 + unnorm + residual', outp, *both(fin)))
+    for what, name, ref64, ref32, ref32f in LC.layer_refs(state_dict, net, st, LC.planes_of(r)):
+        res.append(LC.rule(what, st[name], ref64, ref32, ref32f) if twin else check(what, st[name], ref64, ref32))
+    assert len(res) == 22
     assert_all(res)
+
+
+def test_each_layer_kind(model, weights):
+    each_layer_kind(model, weights, O.golden_unet()['r'], 0)
+
+
+_MODELS = {}
+
+
+def model_of(regime, max_unrolls):
+    """the model of a weight regime of tests/ldamp_cases.py, made once"""
+    if (regime, max_unrolls) not in _MODELS:
+        sd, _ = LC.weights(regime, max_unrolls)
+        _MODELS[regime, max_unrolls] = ldamp.LDAMP(dict(HP, max_unrolls=max_unrolls), device='cuda:0').load_state_dict(sd).eval()
+    return _MODELS[regime, max_unrolls]
+
+
+@pytest.mark.parametrize('case', LC.LAYER_CASES, ids=lambda c: c.name)
+def test_each_layer_kind_under_regimes(case):
+    """Weight scales at which IN_EPS dominates every norm or vanishes, input scales and an offset that ``norm`` has to remove, nets 4
+    and 9 (the offset into the weight block), B = 1 and 5: every stage by the rule."""
+    n = 10 if case.weights == 'plain' else LC.UNROLLS
+    each_layer_kind(model_of(case.weights, n), LC.weights(case.weights, n)[0], LC.layer_input(case), case.net, twin=True)
 
 
 def test_ten_unrolls_against_the_reference(model):
@@ -150,6 +149,104 @@ def test_pilot_counts(model, weights, Np):
         res.append(check('Np %d unroll %d z' % (Np, k), L['z'][k], r64['z'][k], r32['z'][k]))
         res.append(check('Np %d unroll %d div' % (Np, k), L['div'][k], r64['div'][k], r32['div'][k], 'abs'))
     assert_all(res)
+
+
+def run_logs(m, Y, P, eig, d, unrolls=LC.UNROLLS, **kw):
+    H_hat, logs = m(sample_of(Y, P, eig), unrolls, directions=d, return_logs=True, **kw)
+    L = host_logs(logs)
+    L['H_hat'] = H_hat.cpu().numpy()
+    return L
+
+
+@pytest.mark.parametrize('case', LC.LOOP_CASES, ids=lambda c: c.name)
+def test_the_loop_under_regimes(case):
+    """Three unrolls, B = 4, fixed directions: measurements so small that eps sits on its floor (and, at 2^-20, the perturbation is larger
+    than r), large ones, -10 and 30 dB, weights at which IN_EPS dominates.  h, z, div, eps per unroll by the rule."""
+    Y, P, eig, d = LC.loop_problem(case)
+    L = run_logs(model_of(case.weights, LC.UNROLLS), Y, P, eig, d)
+    r64, r32, r32f = LC.loop_refs(case)
+    print('eps: kernel %s, float64 %s' % (L['eps'][:, 0], r64['eps'][:, 0]))
+    if case.floor:                                                    # the floor branch is what ran, at every unroll
+        assert L['eps'].dtype == np.float32 and np.all(L['eps'] == np.float32(LC.EPS_FLOOR)) and np.all(r64['eps'] == LC.EPS_FLOOR)
+    else:
+        assert np.all(L['eps'] > 2 * LC.EPS_FLOOR)
+    res = []
+    for k in range(LC.UNROLLS):
+        for q, kind in (('h', 'norm'), ('z', 'norm'), ('div', 'abs'), ('eps', 'abs')):
+            res.append(LC.rule('%s unroll %d %s' % (case.name, k, q), L[q][k], r64[q][k], r32[q][k], r32f[q][k], kind))
+    assert np.array_equal(L['H_hat'], L['h'][-1])
+    assert_all(res)
+
+
+def test_a_mixed_batch_equals_its_single_sample_calls():
+    """normal, Y x 2^-20, Y x 2^12 and 30 dB in one call: the per-sample eps / stat reductions do not leak between samples"""
+    m = model_of('plain', LC.UNROLLS)
+    Y, P, eig, d = LC.mixed_problem()
+    mixed = run_logs(m, Y, P, eig, d)
+    assert mixed['eps'][0, 1] == np.float32(LC.EPS_FLOOR) and mixed['eps'][0, 2] > 1 and np.all(np.isfinite(mixed['h']))
+    for i in range(4):
+        one = run_logs(m, Y[i:i + 1], P[i:i + 1], eig[i:i + 1], d[:, i:i + 1])
+        for k in ('h', 'z', 'div', 'eps'):
+            assert np.array_equal(one[k][:, 0], mixed[k][:, i]), (i, k)
+        assert np.array_equal(one['H_hat'][0], mixed['H_hat'][i]), i
+
+
+def test_fewer_nets_one_unroll_and_an_empty_batch():
+    ten, three = model_of('plain', 10), model_of('plain', LC.UNROLLS)
+    Y, P, eig, d = LC.loop_problem(LC.MIXED[0])
+    a, b = run_logs(ten, Y, P, eig, d), run_logs(three, Y, P, eig, d)
+    for k in ('h', 'z', 'div', 'eps', 'H_hat'):
+        assert np.array_equal(a[k], b[k]), k                          # the first three nets of ten are the three-net model
+    one = run_logs(ten, Y, P, eig, d[:1], unrolls=1)
+    for k in ('h', 'z', 'div', 'eps'):
+        assert one[k].shape[0] == 1 and np.array_equal(one[k][0], a[k][0]), k
+    assert np.array_equal(one['H_hat'], a['h'][0])
+    with pytest.raises(ValueError, match='num_unrolls'):
+        three(sample_of(Y, P, eig), 4)
+    empty = run_logs(ten, Y[:0], P[:0], eig[:0], d[:, :0])
+    assert empty['H_hat'].shape == (0, 64, 16) and empty['h'].shape == (3, 0, 64, 16) and empty['z'].shape == (3, 0, 38, 16)
+    assert empty['div'].shape == (3, 0) and empty['eps'].shape == (3, 0)
+    assert tuple(ten.denoise(0, dev(np.zeros((0, 64, 16), np.complex64))).shape) == (0, 64, 16)
+
+
+def behind_a_matmul(stream, sources):
+    """Fresh device tensors that become copies of ``sources`` ON ``stream``, queued behind a large matrix product: until that has run
+    they hold zeros, so a launch on another stream would read them unready.  The side stream first waits for the current one."""
+    a = torch.randn(4096, 4096, device='cuda:0')
+    src = [dev(s) for s in sources]
+    out = [torch.zeros_like(s) for s in src]
+    torch.cuda.synchronize()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        b = a @ a
+        b = b @ a
+        for o, s in zip(out, src):
+            o.copy_(s).mul_(2.0).mul_(0.5)
+    return out, b
+
+
+def test_a_callers_stream():
+    m = model_of('plain', LC.UNROLLS)
+    Y, P, eig, d = LC.loop_problem(LC.MIXED[0])
+    r = LC.layer_input(LC.LAYER_CASES[-1])
+    want = run_logs(m, Y, P, eig, d)
+    want_d = m.denoise(1, dev(r)).cpu().numpy()
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    (rs,), keep = behind_a_matmul(side, [r])
+    got_d = m.denoise(1, rs, stream=side)
+    torch.cuda.current_stream().wait_stream(side)
+    assert np.array_equal(got_d.cpu().numpy(), want_d)
+    torch.cuda.synchronize()
+    (Ys, Ps, es, ds), keep = behind_a_matmul(side, [Y, P, eig, d])
+    H_hat, logs = m({'Y_herm': Ys, 'P_herm': Ps, 'eig1': es}, LC.UNROLLS, directions=ds, return_logs=True, stream=side)
+    torch.cuda.current_stream().wait_stream(side)
+    got = host_logs(logs)
+    for k in ('h', 'z', 'div', 'eps'):
+        assert np.array_equal(got[k], want[k]), k
+    assert np.array_equal(H_hat.cpu().numpy(), want['H_hat'])
+    torch.cuda.synchronize()
+    del keep
 
 
 def test_batch_size_and_repetition_do_not_change_a_bit(model):

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import wgan_cases as WC
 import wgan_oracle as O
 from score_based_channels_amd import _lib, wgan
 from score_based_channels_amd import test_wgan as cli
@@ -369,3 +370,143 @@ def test_rejected_settings_raise(fix, net):
         _lib.check(lib.sbc_wgan_create(refs, 1, C.byref(h)))
     # and a refused call leaves the handle usable
     assert tuple(net(z).shape) == (4, 2, 16, 64)
+
+
+# ---- 12. off the fixture: every depth, BatchNorm / latent / problem regimes (tests/wgan_cases.py) ----------------------------------------
+_NETS = {}
+
+
+def net_of(case):
+    key = (case.n_extra, case.bn)
+    if key not in _NETS:
+        _NETS[key] = make_net(WC.state_dict(case)[0])
+    return _NETS[key]
+
+
+def step_of(n, case):
+    """one step of a case on the GPU with every stage of its workspace"""
+    z, Y, P, H, lam, scale = WC.problem(case)
+    got = run(n, z, Y, P, H, 0.01, lam, float(scale), 1)
+    L = 2 + n.n_extra
+    for k in range(L + 1):
+        got['grad%d' % k] = n.stage('grad%d' % k).cpu().numpy()
+    got['act'] = [n.stage('dense').cpu().numpy()] + [n.stage('act%d' % k).cpu().numpy() for k in range(1, L + 1)]
+    got.update(meas=got['meas'][0], reg=got['reg'][0], nmse=got['oracle'][0], g=got['g'][0])
+    return got
+
+
+@pytest.mark.parametrize('case', WC.CASES, ids=lambda c: c.name)
+def test_one_step_under_regimes(case):
+    """The checks the fixture depth has, at every other depth and under the BatchNorm, latent and problem regimes: forward terms, masks,
+    g and dG under the kernel's own masks, every backward layer alone for k = L .. 1, the out adjoint, dG and the dense adjoint alone."""
+    n = net_of(case)
+    sd, _ = WC.state_dict(case)
+    L = 2 + case.n_extra
+    assert n.n_extra == case.n_extra
+    got = step_of(n, case)
+    refs, pre64 = WC.references(case, got['masks'], got['gen'], got['dG'], [got['grad%d' % k] for k in range(L + 1)])
+    assert len(got['masks']) == L and len(refs) == 9 + L
+    assert_masks(got['masks'], pre64)
+    for k in range(1, L + 1):                                                # the activations are what the masks say
+        assert np.array_equal(got['act'][k] > 0, got['masks'][k - 1]), k
+    if case.bn == 'w_zero8':                                                 # a zero weight leaves the BatchNorm bias, exactly
+        for k in range(1, L + 1):
+            b = sd[O.layer_names(k)[1] + '.bias'][WC.ZERO_CHANNELS]
+            assert np.all(got['act'][k][:, WC.ZERO_CHANNELS] == np.maximum(b, 0)[None, :, None, None]), k
+    assert same_bits(got['z_full'][0], WC.problem(case)[0])
+    WC.assert_all([WC.rule('%s %s' % (case.name, what), got[key], r64, r32, r32f, kind) for what, key, kind, r64, r32, r32f in refs])
+
+
+def adam_against_the_formula(what, got, first_step, m0, v0):
+    """z after every step, and m and v after the last, against float64 Adam fed the kernel's own logged gradients"""
+    z_log, g_log = got['z_full'], got['g']
+    steps = len(g_log)
+    z_after = np.concatenate([z_log[1:], got['z'][None]])
+    lr64 = WC.LR.astype(np.float64)[:, None]
+    (r64, m64, v64), (r32, m32, v32) = (O.adam(g_log, z_log[0], lr64, dt, first_step, m0, v0, return_state=True) for dt in (np.float64, np.float32))
+    res = [WC.rule('%s step %d z' % (what, first_step + k), z_after[k], r64[k], r32[k], r32[k]) for k in range(steps)]
+    res.append(WC.rule('%s m' % what, got['m'], m64, m32, m32))
+    res.append(WC.rule('%s v' % what, got['v'], v64, v32, v32))
+    assert got['state']['step'] == first_step - 1 + steps
+    return res
+
+
+@pytest.mark.parametrize('case', WC.ADAM_CASES, ids=lambda c: c.name)
+def test_adam_under_loss_scales(case):
+    """Adam's eps makes the loss scale matter: three steps at scale 1e-3 and 1e3 against the float64 formula on the logged gradients"""
+    z, Y, P, H, lam, scale = WC.problem(case)
+    got = run(net_of(case), z, Y, P, H, WC.LR, lam, float(scale), 3)
+    print('|g| %.2e ... %.2e' % (np.abs(got['g']).min(), np.abs(got['g']).max()))
+    WC.assert_all(adam_against_the_formula(case.name, got, 1, None, None))
+
+
+@pytest.mark.parametrize('first_step', WC.FIRST_STEPS)
+def test_adam_far_from_step_one(first_step):
+    """A run continued at Adam's t = 1000 and 2999 from non-zero moments (v spans 1e-12 ... 1e2), per-sample step sizes, three steps"""
+    case = WC.LATENT_CASES[2]
+    z, Y, P, H, lam, scale = WC.problem(case)
+    m0, v0 = WC.adam_state(first_step)
+    state = {'m': T(m0), 'v': T(v0), 'step': first_step - 1}
+    got = run(net_of(case), z, Y, P, H, WC.LR, lam, float(scale), 3, state=state)
+    assert np.array_equal(state['m'].numpy(), m0) and np.array_equal(state['v'].numpy(), v0)      # the caller's state is not written
+    WC.assert_all(adam_against_the_formula('first step %d' % first_step, got, first_step, m0, v0))
+
+
+@pytest.mark.parametrize('n_extra', range(5))
+def test_workspace_layout_is_the_documented_one(n_extra):
+    """csrc/wgan.hip: one sample's workspace holds, in this order and without gaps, the activations 0 .. L, gen, dG, the gradients L .. 0
+    and the masks 1 .. L; stage offsets scale with B."""
+    n = net_of(WC.Case('layout', n_extra, 'plain', 'plain', 'plain', 0.5, 1.0))
+    L, lib = 2 + n_extra, _lib.lib()
+    order = ['dense'] + ['act%d' % k for k in range(1, L + 1)] + ['gen', 'dG'] + ['grad%d' % k for k in range(L, -1, -1)] + ['mask%d' % k for k in range(1, L + 1)]
+    for B in (1, 3):
+        at = 0
+        for name in order:
+            off, c, h, w = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
+            assert lib.sbc_wgan_stage(n._h, wgan.stage_id(name, n_extra), B, C.byref(off), C.byref(c), C.byref(h), C.byref(w)) == 0
+            assert off.value == at, (B, name, off.value, at)
+            k = int(name[-1]) if name[-1].isdigit() else None
+            want = (2, 16, 64) if name in ('gen', 'dG') else (128, 4, 16) if name in ('dense', 'act0', 'grad0') else \
+                (128, 8 if k == 1 else 16, (32 if k == 1 else 64) // (32 if name.startswith('mask') else 1))
+            assert (c.value, h.value, w.value) == want, (name, c.value, h.value, w.value)
+            at += B * c.value * h.value * w.value
+        assert lib.sbc_wgan_workspace_floats(n._h, B) == at
+
+
+# ---- 13. a caller's stream ------------------------------------------------------------------------------------------------------------------
+def behind_a_matmul(stream, sources):
+    """Fresh device tensors that become copies of ``sources`` ON ``stream``, queued behind a large matrix product: until that has run
+    they hold zeros, so a launch on another stream would read them unready.  The side stream first waits for the current one."""
+    a = torch.randn(4096, 4096, device='cuda:0')
+    src = [T(s).cuda() for s in sources]
+    out = [torch.zeros_like(s) for s in src]
+    torch.cuda.synchronize()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        b = a @ a
+        b = b @ a
+        for o, s in zip(out, src):
+            o.copy_(s).mul_(2.0).mul_(0.5)
+    return out, b
+
+
+def test_a_callers_stream(fix, net):
+    g, _ = fix
+    want_gen = net(T(g['z'])).cpu().numpy()
+    want = run(net, g['z'], g['Y'], g['P'], g['H'], WC.LR[[0, 1, 2, 0]], g['lam'], 0.25, 3)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    (zs,), keep = behind_a_matmul(side, [g['z']])
+    got_gen = net(zs, stream=side)
+    torch.cuda.current_stream().wait_stream(side)
+    assert same_bits(got_gen.cpu().numpy(), want_gen)
+    torch.cuda.synchronize()
+    (zs, Ys, Ps, Hs), keep = behind_a_matmul(side, [g['z'], g['Y'], g['P'], g['H']])
+    zz, st, logs = wgan.LatentOptimizer(net).run(zs, Ys, Ps, WC.LR[[0, 1, 2, 0]], g['lam'], 3, H=Hs, loss_scale=0.25, return_logs='full', stream=side)
+    torch.cuda.current_stream().wait_stream(side)
+    assert same_bits(zz.cpu().numpy(), want['z']) and same_bits(st['m'].cpu().numpy(), want['m']) and same_bits(st['v'].cpu().numpy(), want['v'])
+    for k, name in (('meas', 'meas'), ('reg', 'reg'), ('oracle', 'oracle'), ('g', 'g'), ('z', 'z_full')):
+        assert same_bits(logs[k].cpu().numpy(), want[name]), k
+    assert same_bits(zs.cpu().numpy(), g['z'])                               # the caller's latents are not written
+    torch.cuda.synchronize()
+    del keep

@@ -115,3 +115,80 @@ def test_cli_parsing_and_result_layout(tmp_path, monkeypatch):
         # the loader added noise of std 10^(-snr/20) sqrt(64) per complex entry (:83)
         resid = batch['Y_herm'] - batch['P_herm'] @ batch['H_herm_cplx']
         assert abs(np.sqrt(np.mean(np.abs(resid) ** 2)) / (10 ** (-snr / 20) * 8) - 1) < 0.05
+
+
+# ---- the regimes of tests/ldamp_cases.py: are they reached, and can the rule test them? -----------------------------------------------
+import ldamp_cases as LC  # noqa: E402
+
+F32, F64 = torch.float32, torch.float64
+
+
+def _twin_is_the_identity_in_float64(sd, fsd, net, r):
+    x = torch.from_numpy(LC.planes_of(r)).double()
+    with torch.no_grad():
+        a, b = O.denoise_planes(sd, net, x, F64), O.denoise_planes_flipped(fsd, net, x, F64)
+        a32, b32 = O.denoise_planes(sd, net, x.float(), F32), O.denoise_planes_flipped(fsd, net, x.float(), F32)
+    d = O.normwise(b.numpy(), a.numpy())
+    print('flipped twin against native: float64 %.2e, float32 same bits: %s' % (d, bool(torch.equal(a32, b32))))
+    assert d < 1e-12
+    assert not torch.equal(a32, b32)                                  # and in float32 it is another order, not the same one
+
+
+@pytest.mark.parametrize('case', LC.LAYER_CASES, ids=lambda c: c.name)
+def test_layer_case_reaches_its_regime_and_the_reference_satisfies_the_rule(case):
+    """The float32 oracle's stages stand in for the kernel's: every layer's input from them goes through the layer in float64 and in
+    the two float32 orders."""
+    sd, fsd = LC.weights(case.weights, 10 if case.weights == 'plain' else LC.UNROLLS)
+    r = LC.layer_input(case)
+    assert r.shape == (case.B, 64, 16) and np.all(np.isfinite(r.view(np.float32)))
+    st = LC.oracle_stages(sd, case.net, r)
+    if case.weights != 'plain':
+        var = np.concatenate([v.ravel() for v in LC.conv_variances(sd, case.net, st)])
+        share = float(np.mean(var < LC.IN_EPS))
+        print('share of channels with variance below IN_EPS: %.3f (variance %.2e ... %.2e)' % (share, var.min(), var.max()))
+        assert (share > 0.9) if case.weights == 'w_2m10' else (share == 0 if case.weights == 'w_2p8' else 0 < share < 1)
+    if case.input == 'in_offset':
+        ratio = np.abs(st['stat'][:, [0, 2]]) / st['stat'][:, [1, 3]]
+        print('|mean| / std of the planes: %.1f ... %.1f' % (ratio.min(), ratio.max()))
+        assert np.all(ratio > 20)
+    if case.input in ('in_2m20', 'in_2p12'):
+        base = LC.oracle_stages(sd, case.net, LC.layer_input(case._replace(input='plain')))
+        assert np.array_equal(st['x'], base['x'])                     # a power of two: norm removes it exactly
+    LC.assert_all([LC.mutual(what, ref64, a, b) for what, _, ref64, a, b in LC.layer_refs(sd, case.net, st, LC.planes_of(r))])
+    _twin_is_the_identity_in_float64(sd, fsd, case.net, r)
+
+
+@pytest.mark.parametrize('case', LC.MIXED[:1] + LC.LOOP_CASES, ids=lambda c: c.name)
+def test_loop_case_reaches_its_regime_and_the_reference_satisfies_the_rule(case):
+    r64, r32, r32f = LC.loop_refs(case)
+    Y, P, eig, d = LC.loop_problem(case)
+    r0 = np.conj(np.transpose(P, (0, 2, 1))) @ Y / eig[:, None, None]
+    print('max|r| at unroll 0: %.2e; eps %s' % (np.abs(r0).max(), r64['eps'][:, 0]))
+    if case.floor:
+        for k in range(LC.UNROLLS):                                   # the floor branch at EVERY unroll, in both precisions
+            assert np.all(r64['eps'][k] == LC.EPS_FLOOR) and np.all(r32['eps'][k] == np.float32(LC.EPS_FLOOR)), k
+            assert np.all(r32f['eps'][k] == np.float32(LC.EPS_FLOOR)), k
+        assert np.abs(r0).max() < 1e-2
+    else:
+        assert np.all(r64['eps'] > 2 * LC.EPS_FLOOR)
+    if case.name == 'y_2m20':
+        assert np.abs(r0).max() < LC.EPS_FLOOR                        # |eps d| ~ eps: the perturbation is larger than r itself
+    res = []
+    for k in range(LC.UNROLLS):
+        res.append(LC.mutual('%s unroll %d h' % (case.name, k), r64['h'][k], r32['h'][k], r32f['h'][k]))
+        res.append(LC.mutual('%s unroll %d z' % (case.name, k), r64['z'][k], r32['z'][k], r32f['z'][k]))
+        res.append(LC.mutual('%s unroll %d div' % (case.name, k), r64['div'][k], r32['div'][k], r32f['div'][k], 'abs'))
+        res.append(LC.mutual('%s unroll %d eps' % (case.name, k), r64['eps'][k], r32['eps'][k], r32f['eps'][k], 'abs'))
+    LC.assert_all(res)
+    sd, fsd = LC.weights(case.weights, LC.UNROLLS)
+    _twin_is_the_identity_in_float64(sd, fsd, 0, r0.astype(np.complex64))
+
+
+def test_the_mixed_batch_is_one_sample_of_each_regime():
+    Y, P, eig, d = LC.mixed_problem()
+    assert Y.shape == (4, 38, 16) and d.shape == (3, 4, 64, 16, 2)
+    for i, c in enumerate(LC.MIXED):
+        Yc, Pc, eigc, dc = LC.loop_problem(c)
+        assert np.array_equal(Y[i], Yc[i]) and np.array_equal(P[i], Pc[i]) and eig[i] == eigc[i] and np.array_equal(d, dc)
+    amp = np.abs(Y).max(axis=(1, 2))
+    assert amp[1] < 1e-4 * amp[0] and amp[2] > 1e3 * amp[0]

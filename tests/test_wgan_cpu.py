@@ -184,3 +184,96 @@ def test_cli_file_contract_with_an_injected_estimate(tmp_path, monkeypatch):
     assert os.path.exists('wgan_CDL-D_0.50/extra1/wgan_results_modelCDL-D_channelCDL-D_DETAILED.pt')
     with pytest.raises(FileNotFoundError):
         cli.main(['--synthetic', '--model', 'CDL-A'], estimate_fn=_fake_estimate(calls))
+
+
+# ---- the regimes of tests/wgan_cases.py: are they reached, and can the rule test them? -------------------------------------------------
+import wgan_cases as WC  # noqa: E402
+
+F32, F64 = torch.float32, torch.float64
+
+
+def _regime_is_reached(case, sd, stand_in):
+    plain = wgan.seeded_state_dict(WC.SEED_WEIGHTS, case.n_extra)
+    assert O.n_layers(sd) == 2 + case.n_extra and wgan.n_extra_of(sd) == case.n_extra
+    z, Y, P, H, lam, scale = WC.problem(case)
+    for k in range(1, O.n_layers(sd) + 1):
+        bn = O.layer_names(k)[1]
+        var, w = sd[bn + '.running_var'], sd[bn + '.weight']
+        if case.bn == 'var_1em4':
+            assert np.all(var > 5 * O.BN_EPS) and np.all(var < 2e-4) and np.array_equal(var, plain[bn + '.running_var'] * np.float32(1e-4))
+        if case.bn == 'w_1em2_signed':
+            assert np.all(w[::3] < 0) and np.all(np.delete(w, np.arange(0, 128, 3)) > 0) and np.all(np.abs(w) < 0.013) and np.all(np.abs(w) > 0.007)
+        if case.bn == 'w_zero8':
+            assert np.count_nonzero(w == 0) == 8 and np.all(w[WC.ZERO_CHANNELS] == 0)
+            pre = stand_in['pre'][k - 1][:, WC.ZERO_CHANNELS]
+            assert np.all(pre == sd[bn + '.bias'][WC.ZERO_CHANNELS][None, :, None, None])         # the activation is constant
+            g = np.zeros_like(stand_in['grad'][k])
+            g[:, WC.ZERO_CHANNELS] = stand_in['grad'][k][:, WC.ZERO_CHANNELS]
+            assert not np.any(O.layer_vjp(sd, k, g, stand_in['masks'][k - 1], F64))                # and nothing flows back through it
+        if case.bn == 'plain':
+            assert np.all(var > 0.5) and np.all(w > 0.7)
+    assert np.array_equal(z, {'plain': O.init_z(WC.B), 'zero': np.zeros((WC.B, 60), np.float32), 'times8': 8 * O.init_z(WC.B)}[case.z])
+    assert np.array_equal(lam, np.zeros(3, np.float32) if case.lam == 'zero' else WC.LAM) and scale == np.float32(case.scale)
+    Y1 = WC.problem(case._replace(y_scale=1.0))[1]
+    assert np.allclose(Y, Y1 * case.y_scale, rtol=1e-6, atol=0) and np.all(np.isfinite(Y.view(np.float32)))
+
+
+@pytest.mark.parametrize('case', WC.CASES, ids=lambda c: c.name)
+def test_step_case_reaches_its_regime_and_the_reference_satisfies_the_rule(case):
+    """A float32 oracle's own masks, gen, dG and backward chain stand in for the kernel's."""
+    sd, fsd = WC.state_dict(case)
+    own = WC.oracle_step(case)
+    _regime_is_reached(case, sd, own)
+    refs, pre64 = WC.references(case, own['masks'], own['gen'], own['dG'], own['grad'])
+    assert len(refs) == 9 + O.n_layers(sd)
+    res = [WC.mutual('%s %s' % (case.name, what), r64, r32, r32f, kind) for what, _, kind, r64, r32, r32f in refs]
+    # masks: both float32 orders' pre-activations lie within 1e-5 rms of float64's on every layer, a margin of 10 under the 1e-4 band
+    z, Y, P, H, lam, scale = WC.problem(case)
+    flipped = O.forward_terms(fsd, z, Y, P, H, F32, O.generate_flipped)['pre']
+    for name, pre in (('native', own['pre']), ('flipped', flipped)):
+        dist = WC.pre_distance(pre, pre64)
+        print('%s pre-activations from float64, in rms of the layer: %s' % (name, ['%.2e' % d for d in dist]))
+        assert max(dist) < 1e-5, (name, dist)
+    # the flipped twin is the identity in float64
+    a = O.step_terms(sd, z, Y, P, H, lam, scale, F64, own['masks'])
+    b = O.step_terms(fsd, z, Y, P, H, lam, scale, F64, own['masks'], O.generate_flipped)
+    for k in ('gen', 'g', 'dG'):
+        d = O.normwise(b[k], a[k])
+        print('flipped twin against native in float64, %s: %.2e' % (k, d))
+        assert d < 1e-12, (k, d)
+    L = O.n_layers(sd)
+    assert O.normwise(O.layer_vjp_flipped(fsd, L, own['grad'][L], own['masks'][L - 1], F64), O.layer_vjp(sd, L, own['grad'][L], own['masks'][L - 1], F64)) < 1e-12
+    assert O.normwise(O.out_vjp_flipped(fsd, own['dG'], F64), O.out_vjp(sd, own['dG'], F64)) < 1e-12
+    assert O.normwise(O.dense_vjp_flipped(fsd, own['grad'][0], F64), O.dense_vjp(sd, own['grad'][0], F64)) < 1e-12
+    s = np.full(WC.B, scale, np.float32)
+    assert O.normwise(O.residual_vjp_flipped(own['gen'], Y, P, s, F64), O.residual_vjp(own['gen'], Y, P, s, F64)) < 1e-12
+    WC.assert_all(res)
+
+
+@pytest.mark.parametrize('first_step', WC.FIRST_STEPS)
+def test_oracle_adam_continues_torch_adam(first_step):
+    """``O.adam`` with ``first_step`` and initial moments is ``torch.optim.Adam`` continued from the same state, per-sample step sizes
+    as one optimiser per sample."""
+    m0, v0 = WC.adam_state(first_step)
+    assert np.all(v0 > 0) and v0.min() < 1e-11 and v0.max() > 10 and np.count_nonzero(m0) == m0.size
+    rng = np.random.default_rng(first_step + 1)
+    z0, gs = rng.standard_normal((WC.B, 60)), rng.standard_normal((3, WC.B, 60)) * np.sqrt(v0)[None]
+    for dtype, tol in ((np.float64, 1e-13), (np.float32, 3e-7)):
+        got, m, v = O.adam(gs, z0, WC.LR.astype(np.float64)[:, None], dtype, first_step, m0, v0, return_state=True)
+        assert got.dtype == dtype and got.shape == (3, WC.B, 60)
+        for b in range(WC.B):
+            p = torch.tensor(z0[b].astype(dtype), requires_grad=True)
+            opt = torch.optim.Adam([p], lr=float(WC.LR[b]))
+            opt.state[p] = {'step': torch.tensor(float(first_step - 1)), 'exp_avg': torch.tensor(m0[b].astype(dtype)),
+                            'exp_avg_sq': torch.tensor(v0[b].astype(dtype))}
+            for k, g in enumerate(gs):
+                p.grad = torch.from_numpy(g[b].astype(dtype))
+                opt.step()
+                assert O.normwise(got[k, b][None], p.detach().numpy()[None]) <= tol, (dtype, b, k)
+            assert float(opt.state[p]['step']) == first_step + 2
+            assert O.normwise(m[b][None], opt.state[p]['exp_avg'].numpy()[None]) <= tol
+            assert O.normwise(v[b][None], opt.state[p]['exp_avg_sq'].numpy()[None]) <= tol
+    # from step 1 with zero moments it is the helper as it was
+    assert np.array_equal(O.adam(gs, z0, 0.01, np.float64, 1, np.zeros_like(z0), np.zeros_like(z0)), O.adam(gs, z0, 0.01, np.float64))
+    # and the bias corrections matter at these steps: Adam's t = 1 .. 3 gives another iterate
+    assert O.normwise(O.adam(gs, z0, 0.01, np.float64, 1, m0, v0), O.adam(gs, z0, 0.01, np.float64, first_step, m0, v0)) > 1e-4

@@ -6,7 +6,8 @@ UNDER ITS OWN masks, and its masks with float64's only away from zero.
 
     generate(sd, z, dtype, masks=None)                      -> gen [B, 2, 16, 64], pre-activations [L x [B, 128, H, W]], activations
     step_terms(sd, z, Y, P, H, lam, scale, dtype, masks)    -> dict gen, meas, reg, nmse, g (= d sum_b scale_b (meas_b + lam_b reg_b) / d z)
-    adam(g_history, z0, lr, dtype)                          -> the iterates z_1 .. z_K of torch.optim.Adam's defaults fed these gradients
+    adam(g_history, z0, lr, dtype, first_step, m0, v0)      -> the iterates z_1 .. z_K of torch.optim.Adam's defaults fed these gradients
+    flip_state_dict / generate_flipped / *_vjp_flipped      -> the same functions in another summation order (the spatially flipped twin)
 """
 import os
 
@@ -93,13 +94,14 @@ def loss_terms(gen, z, Y, P, H, dtype):
     return meas, reg, nmse
 
 
-def step_terms(sd, z, Y, P, H, lam, scale, dtype, masks=None):
-    """One evaluation at z [B, 60]: numpy dict gen, meas, reg, nmse, g, dG (= d loss / d gen) and the pre-activations ``pre``."""
+def step_terms(sd, z, Y, P, H, lam, scale, dtype, masks=None, gen_fn=None):
+    """One evaluation at z [B, 60]: numpy dict gen, meas, reg, nmse, g, dG (= d loss / d gen) and the pre-activations ``pre``.
+    ``gen_fn``: another evaluation order of the generator (``generate_flipped`` with ``sd`` a ``flip_state_dict``)."""
     z = _t(np.asarray(z).reshape(-1, NZ), dtype).requires_grad_(True)
     B = z.shape[0]
     lam = _t(np.broadcast_to(np.asarray(lam, np.float64), (B,)).copy(), dtype)
     scale = _t(np.broadcast_to(np.asarray(scale, np.float64), (B,)).copy(), dtype)
-    gen, pres, _ = generate(sd, z, dtype, masks)
+    gen, pres, _ = (gen_fn or generate)(sd, z, dtype, masks)
     gen.retain_grad()
     meas, reg, nmse = loss_terms(gen, z, Y, P, H, dtype)
     loss = torch.sum(scale * (meas + lam * reg))
@@ -134,11 +136,11 @@ def residual_vjp(gen, Y, P, scale, dtype):
     return torch.autograd.grad(torch.sum(_t(np.asarray(scale, np.float64), dtype) * meas), x)[0].numpy()
 
 
-def forward_terms(sd, z, Y, P, H, dtype):
+def forward_terms(sd, z, Y, P, H, dtype, gen_fn=None):
     """gen, meas, reg, nmse and the pre-activations at z, without the backward pass"""
     with torch.no_grad():
         zt = _t(np.asarray(z).reshape(-1, NZ), dtype)
-        gen, pres, _ = generate(sd, zt, dtype)
+        gen, pres, _ = (gen_fn or generate)(sd, zt, dtype)
         meas, reg, nmse = loss_terms(gen, zt, Y, P, H, dtype)
     return {'gen': gen.numpy(), 'meas': meas.numpy(), 'reg': reg.numpy(), 'nmse': nmse.numpy(), 'pre': [p.numpy() for p in pres]}
 
@@ -148,24 +150,71 @@ def dense_vjp(sd, g0, dtype):
     return (_t(g0, dtype).reshape(-1, 8192) @ _t(sd['dense.dense_input.weight'], dtype)).numpy()
 
 
-def adam(g_history, z0, lr, dtype):
-    """The iterates z_1 .. z_K [K, ...] of ``torch.optim.Adam`` (betas 0.9 / 0.999, eps 1e-8, bias correction) started at ``z0`` with
-    zero moments and fed the gradients ``g_history`` [K, ...]; every operation in ``dtype``, the scalars formed in float64 first as
-    torch forms them.  ``lr``: a scalar or an array broadcastable against z (float64)."""
+def adam(g_history, z0, lr, dtype, first_step=1, m0=None, v0=None, return_state=False):
+    """The iterates z_1 .. z_K [K, ...] of ``torch.optim.Adam`` (betas 0.9 / 0.999, eps 1e-8, bias correction) started at ``z0`` and fed
+    the gradients ``g_history`` [K, ...]; every operation in ``dtype``, the scalars formed in float64 first as torch forms them.
+    ``lr``: a scalar or an array broadcastable against z (float64).  A run is continued with ``first_step`` (Adam's t of the first
+    gradient) and the moments ``m0``, ``v0`` it had reached; ``return_state``: also the moments after the last step."""
     dt = np.dtype(dtype)
     z = np.asarray(z0, dt).copy()
-    m, v = np.zeros_like(z), np.zeros_like(z)
+    m = np.zeros_like(z) if m0 is None else np.asarray(m0, dt).copy()
+    v = np.zeros_like(z) if v0 is None else np.asarray(v0, dt).copy()
     b1, b2 = 0.9, 0.999
     w1, c2, w2, eps = dt.type(1.0 - b1), dt.type(b2), dt.type(1.0 - b2), dt.type(1e-8)
     out = []
-    for t, g in enumerate(np.asarray(g_history, dt), start=1):
+    for t, g in enumerate(np.asarray(g_history, dt), start=int(first_step)):
         m = m + (g - m) * w1
         v = v * c2 + (w2 * g) * g
         denom = np.sqrt(v) / dt.type(np.sqrt(1.0 - b2 ** t)) + eps
         step = (np.asarray(lr, np.float64) / (1.0 - b1 ** t)).astype(dt)
         z = z - step * (m / denom)
         out.append(z.copy())
-    return np.stack(out)
+    return (np.stack(out), m, v) if return_state else np.stack(out)
+
+
+# ---- the flipped twin: the same function in another valid summation order ---------------------------------------------------------
+# Every 5 x 5 / 3 x 3 filter flipped in its last two axes, the dense rows and bias permuted to the flipped [128, 4, 16] view, the masks
+# flipped, every output flipped back.  Nearest x 2, the convolutions, BatchNorm and ReLU commute with the flip, so in exact arithmetic the
+# twin is the identity; in float32 its sums run in another order.
+def flip(x):
+    return torch.flip(x, (-2, -1)) if isinstance(x, torch.Tensor) else np.asarray(x)[..., ::-1, ::-1].copy()
+
+
+def flip_state_dict(sd):
+    out = {}
+    for k, v in sd.items():
+        v = np.asarray(v)
+        if v.ndim == 4:
+            v = v[..., ::-1, ::-1].copy()
+        elif k == 'dense.dense_input.weight':
+            v = v.reshape(128, NR // 4, NT // 4, NZ)[:, ::-1, ::-1].reshape(-1, NZ).copy()
+        elif k == 'dense.dense_input.bias':
+            v = v.reshape(128, NR // 4, NT // 4)[:, ::-1, ::-1].reshape(-1).copy()
+        out[k] = v
+    return out
+
+
+def generate_flipped(fsd, z, dtype, masks=None):
+    """``generate`` through the twin; ``fsd = flip_state_dict(sd)``"""
+    gen, pres, acts = generate(fsd, z, dtype, None if masks is None else [flip(np.asarray(m)) for m in masks])
+    return flip(gen), [flip(p) for p in pres], [flip(a) for a in acts]
+
+
+def layer_vjp_flipped(fsd, k, grad_out, mask, dtype):
+    return flip(layer_vjp(fsd, k, flip(np.asarray(grad_out)), flip(np.asarray(mask)), dtype))
+
+
+def out_vjp_flipped(fsd, dG, dtype):
+    return flip(out_vjp(fsd, flip(np.asarray(dG)), dtype))
+
+
+def dense_vjp_flipped(fsd, g0, dtype):
+    return dense_vjp(fsd, flip(np.asarray(g0)), dtype)
+
+
+def residual_vjp_flipped(gen, Y, P, scale, dtype):
+    """the antenna axes reversed (receive rows of G and Y, transmit columns of G = rows of P): the sums over t run the other way"""
+    return flip(residual_vjp(flip(np.asarray(gen)), np.asarray(Y)[:, ::-1].copy(), np.asarray(P)[:, ::-1].copy(), scale, dtype))
 
 
 def normwise(a, ref):
