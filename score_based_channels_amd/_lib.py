@@ -193,6 +193,101 @@ def check(rc):
         raise SbcError('libsbc_hip: %s (status %d)' % (lib().sbc_last_error().decode(), rc))
 
 
+def check_against_spec(sd, spec):
+    """Raise ``KeyError`` / ``ValueError`` like ``load_state_dict(strict=True)`` would; ``spec``: ordered ``[(name, shape)]``."""
+    import numpy as np
+    names = dict(spec)
+    missing = [n for n, _ in spec if n not in sd]
+    unexpected = [n for n in sd if n not in names]
+    if missing or unexpected:
+        raise KeyError('state_dict mismatch: missing %s, unexpected %s' % (missing[:5], unexpected[:5]))
+    for n, shape in spec:
+        if tuple(np.shape(sd[n])) != tuple(shape):
+            raise ValueError('size mismatch for %s: %s vs %s' % (n, tuple(np.shape(sd[n])), tuple(shape)))
+
+
+def tensor_refs(sd, names):
+    """``(sbc_tensor_ref[len(names)], keepalive)`` over ``sd[name]`` as contiguous float32 host arrays.  The refs hold bare pointers:
+    ``keepalive`` must outlive the call they are passed to."""
+    import numpy as np
+    names = list(names)
+    keep = [np.ascontiguousarray(sd[n], dtype=np.float32) for n in names]
+    enc = [n.encode() for n in names]
+    refs = (sbc_tensor_ref * len(names))(*[sbc_tensor_ref(enc[i], a.ctypes.data_as(C.c_void_p), a.size) for i, a in enumerate(keep)])
+    return refs, (keep, enc)
+
+
+class DeviceHandle:
+    """Base of the classes that own one library handle with its weights on a torch device (``ldamp.LDAMP``,
+    ``wgan.DCGAN_G_Ours``): device resolution, the grow-only workspace tensor and the handle's lifetime.  A subclass names the
+    library function that frees its handle in ``_destroy``."""
+    _destroy = None
+
+    def __init__(self, device=None):
+        self.device = device
+        self._h = None
+        self._ws = None
+        self.last_workspace = None                       # (tensor, n_images) of the last call, for stage()
+
+    def cuda(self, device=None):
+        self.device = device if device is not None else self.device
+        return self
+
+    def eval(self):
+        return self
+
+    def _torch_device(self):
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError('%s needs a HIP device (there is no CPU fallback)' % type(self).__name__)
+        d = self.device
+        if d is None:
+            return torch.device('cuda', torch.cuda.current_device())
+        d = torch.device(d)
+        return d if d.index is not None else torch.device('cuda', torch.cuda.current_device())
+
+    def _need_weights(self):
+        if self._h is None:
+            raise RuntimeError('%s has no weights: call load_state_dict first' % type(self).__name__)
+
+    def _load(self, sd, names, create):
+        """Replace the handle by the one ``create(refs, len(names), byref(handle))`` makes of ``sd``'s tensors ``names`` on this
+        object's device; the old handle is freed only once the new one exists."""
+        import torch
+        refs, keep = tensor_refs(sd, names)              # (keep: the host arrays, alive until create has copied them)
+        handle = C.c_void_p()
+        with torch.cuda.device(self._torch_device()):
+            check(create(refs, len(refs), C.byref(handle)))
+        self.close()
+        self._h = handle
+        return self
+
+    def _workspace_of(self, n, dev):
+        """The workspace tensor, re-allocated only when ``n`` floats do not fit or the device changed."""
+        import torch
+        if self._ws is None or self._ws.numel() < n or self._ws.device != dev:
+            self._ws = None                              # (released before its replacement is allocated)
+            self._ws = torch.empty(max(int(n), 1), dtype=torch.float32, device=dev)
+        return self._ws
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def numpy_state_dict(state):
+    """A ``state_dict`` of torch tensors and / or array-likes as ``{name: numpy array}`` on the host."""
+    import numpy as np
+    return {k: (v.detach().cpu().numpy() if hasattr(v, 'detach') else np.asarray(v)) for k, v in state.items()}
+
+
 RANGE_OVERFLOW, RANGE_UNDERFLOW, RANGE_ELU = 1, 2, 4
 
 

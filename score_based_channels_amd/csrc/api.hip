@@ -636,230 +636,51 @@ int sbc_plan_profile_read(sbc_plan* plan, double* total_ms, int64_t* n_launches)
     return SBC_OK;
 }
 
-int sbc_pack_conv_weight(const float* src, int32_t cout, int32_t cin, int32_t ksize, float* dst) {
-    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight: NULL pointer");
-    SBC_REQUIRE(cin % 8 == 0 && cout % 32 == 0 && (ksize == 1 || ksize == 3),
-                "sbc_pack_conv_weight: cin %% 8, cout %% 32, ksize in {1,3} required (got %d, %d, %d)", cin, cout, ksize);
-    const int taps = ksize * ksize, KG = cin / 8, NB = cout / 32;
+}  // extern "C"
+
+// ---- weight packers: torch [cout][cin][taps] float32 -> MFMA B-operand fragments -----------------------------------------
+// One walk for every form.  A K group is 2 * KPACK input channels: lanes 0-31 of a wavefront hold the first KPACK of them for output
+// channel nb * 32 + lane, lanes 32-63 the second KPACK (fp32: 4 values = one 16-byte load per lane; 16-bit forms: 8).  `enc` turns one
+// weight into its TERMS stored values; the terms of a fragment lie behind one another:
+//     dst[((((tap * KG + g) * NB + nb) * TERMS + term) * 64 + lane) * KPACK + j]
+namespace {
+
+template <int KPACK, int TERMS, typename T, typename Enc>
+void pack_fragments(const float* src, int cout, int cin, int taps, T* dst, Enc enc) {
+    const int KG = cin / (2 * KPACK), NB = cout / 32;
     for (int tap = 0; tap < taps; ++tap)
         for (int g = 0; g < KG; ++g)
             for (int nb = 0; nb < NB; ++nb)
                 for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j) {
-                        const int co = nb * 32 + (lane & 31), ci = g * 8 + 4 * (lane >> 5) + j;
-                        dst[((((size_t)tap * KG + g) * NB + nb) * 64 + lane) * 4 + j] =
-                            src[((size_t)co * cin + ci) * taps + tap];
+                    for (int j = 0; j < KPACK; ++j) {
+                        const int co = nb * 32 + (lane & 31), ci = g * 2 * KPACK + KPACK * (lane >> 5) + j;
+                        T term[TERMS];
+                        enc(src[((size_t)co * cin + ci) * taps + tap], term);
+                        const size_t base = (((size_t)tap * KG + g) * NB + nb) * TERMS;
+                        for (int t = 0; t < TERMS; ++t) dst[((base + t) * 64 + lane) * KPACK + j] = term[t];
                     }
-    return SBC_OK;
 }
 
-int sbc_pack_conv_weight_winograd(const float* src, int32_t cout, int32_t cin, float* dst) {
-    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_winograd: NULL pointer");
-    SBC_REQUIRE(cin % 8 == 0 && cout % 32 == 0, "sbc_pack_conv_weight_winograd: cin %% 8, cout %% 32 required (got %d, %d)",
-                cin, cout);
+// Winograd F(2x2, 3x3) filter transform U = G g G^T of [cout][cin][3][3], summed in double and rounded once: [cout][cin][16]
+std::vector<float> winograd_u(const float* src, int cout, int cin) {
     static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
     std::vector<float> u((size_t)cout * cin * 16);
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci) {
-            const float* g = src + ((size_t)co * cin + ci) * 9;
-            for (int i = 0; i < 4; ++i)
-                for (int l = 0; l < 4; ++l) {
-                    double s = 0;
-                    for (int j = 0; j < 3; ++j)
-                        for (int k = 0; k < 3; ++k) s += G[i][j] * (double)g[j * 3 + k] * G[l][k];
-                    u[((size_t)co * cin + ci) * 16 + i * 4 + l] = (float)s;
-                }
-        }
-    const int KG = cin / 8, NB = cout / 32;
-    for (int tap = 0; tap < 16; ++tap)
-        for (int g = 0; g < KG; ++g)
-            for (int nb = 0; nb < NB; ++nb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j) {
-                        const int co = nb * 32 + (lane & 31), ci = g * 8 + 4 * (lane >> 5) + j;
-                        dst[((((size_t)tap * KG + g) * NB + nb) * 64 + lane) * 4 + j] = u[((size_t)co * cin + ci) * 16 + tap];
-                    }
-    return SBC_OK;
-}
-
-// round-to-nearest-even fp32 -> bf16 (bit pattern), as v_cvt_pk_bf16_f32 does for finite values
-static inline uint16_t bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static inline float bf16_to_f32(uint16_t b) {
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-int sbc_pack_conv_weight_split(const float* src, int32_t cout, int32_t cin, int32_t ksize, uint16_t* dst) {
-    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_split: NULL pointer");
-    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0 && (ksize == 1 || ksize == 3),
-                "sbc_pack_conv_weight_split: cin %% 16, cout %% 32, ksize in {1,3} required (got %d, %d, %d)", cin, cout,
-                ksize);
-    const int taps = ksize * ksize, KG = cin / 16, NB = cout / 32;
-    for (int tap = 0; tap < taps; ++tap)
-        for (int g = 0; g < KG; ++g)
-            for (int nb = 0; nb < NB; ++nb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int co = nb * 32 + (lane & 31), ci = g * 16 + 8 * (lane >> 5) + j;
-                        const float w = src[((size_t)co * cin + ci) * taps + tap];
-                        const uint16_t h = bf16_rne(w);
-                        const float r1 = w - bf16_to_f32(h);
-                        const uint16_t m = bf16_rne(r1);
-                        const uint16_t l = bf16_rne(r1 - bf16_to_f32(m));
-                        const size_t base = (((size_t)tap * KG + g) * NB + nb) * 3;
-                        dst[((base + 0) * 64 + lane) * 8 + j] = h;
-                        dst[((base + 1) * 64 + lane) * 8 + j] = m;
-                        dst[((base + 2) * 64 + lane) * 8 + j] = l;
-                    }
-    return SBC_OK;
-}
-
-int sbc_pack_conv_weight_winograd_split(const float* src, int32_t cout, int32_t cin, uint16_t* dst) {
-    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_winograd_split: NULL pointer");
-    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0, "sbc_pack_conv_weight_winograd_split: cin %% 16, cout %% 32 required (got %d, %d)",
-                cin, cout);
-    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    std::vector<float> u((size_t)cout * cin * 16);             // torch-like [cout][cin][4][4]
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci) {
-            const float* g = src + ((size_t)co * cin + ci) * 9;
-            for (int i = 0; i < 4; ++i)
-                for (int l = 0; l < 4; ++l) {
-                    double s = 0;
-                    for (int j = 0; j < 3; ++j)
-                        for (int k = 0; k < 3; ++k) s += G[i][j] * (double)g[j * 3 + k] * G[l][k];
-                    u[((size_t)co * cin + ci) * 16 + i * 4 + l] = (float)s;
-                }
-        }
-    const int KG = cin / 16, NB = cout / 32;
-    for (int tap = 0; tap < 16; ++tap)
-        for (int g = 0; g < KG; ++g)
-            for (int nb = 0; nb < NB; ++nb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int co = nb * 32 + (lane & 31), ci = g * 16 + 8 * (lane >> 5) + j;
-                        const float w = u[((size_t)co * cin + ci) * 16 + tap];
-                        const uint16_t h = bf16_rne(w);
-                        const float r1 = w - bf16_to_f32(h);
-                        const uint16_t m = bf16_rne(r1);
-                        const uint16_t l = bf16_rne(r1 - bf16_to_f32(m));
-                        const size_t base = (((size_t)tap * KG + g) * NB + nb) * 3;
-                        dst[((base + 0) * 64 + lane) * 8 + j] = h;
-                        dst[((base + 1) * 64 + lane) * 8 + j] = m;
-                        dst[((base + 2) * 64 + lane) * 8 + j] = l;
-                    }
-    return SBC_OK;
-}
-
-// round-to-nearest-even fp32 -> fp16 bit pattern (the host compiler's _Float16 conversion is IEEE RNE, like v_cvt_f16_f32)
-static inline uint16_t f16_rne(float f) {
-    const _Float16 h = (_Float16)f;
-    uint16_t u;
-    memcpy(&u, &h, 2);
+    for (size_t oc = 0; oc < (size_t)cout * cin; ++oc) {
+        const float* g = src + oc * 9;
+        for (int i = 0; i < 4; ++i)
+            for (int l = 0; l < 4; ++l) {
+                double s = 0;
+                for (int j = 0; j < 3; ++j)
+                    for (int k = 0; k < 3; ++k) s += G[i][j] * (double)g[j * 3 + k] * G[l][k];
+                u[oc * 16 + i * 4 + l] = (float)s;
+            }
+    }
     return u;
 }
 
-int sbc_pack_conv_weight_f16(const float* src, int32_t cout, int32_t cin, int32_t ksize, uint16_t* dst) {
-    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_f16: NULL pointer");
-    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0 && (ksize == 1 || ksize == 3),
-                "sbc_pack_conv_weight_f16: cin %% 16, cout %% 32, ksize in {1,3} required (got %d, %d, %d)", cin, cout, ksize);
-    const int taps = ksize * ksize, KG = cin / 16, NB = cout / 32;
-    for (int tap = 0; tap < taps; ++tap)
-        for (int g = 0; g < KG; ++g)
-            for (int nb = 0; nb < NB; ++nb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int co = nb * 32 + (lane & 31), ci = g * 16 + 8 * (lane >> 5) + j;
-                        dst[((((size_t)tap * KG + g) * NB + nb) * 64 + lane) * 8 + j] =
-                            f16_rne(src[((size_t)co * cin + ci) * taps + tap]);
-                    }
-    return SBC_OK;
-}
-
-int sbc_pack_conv_weight_winograd_f16(const float* src, int32_t cout, int32_t cin, uint16_t* dst) {
-    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_winograd_f16: NULL pointer");
-    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0, "sbc_pack_conv_weight_winograd_f16: cin %% 16, cout %% 32 required (got %d, %d)",
-                cin, cout);
-    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    const int KG = cin / 16, NB = cout / 32;
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci) {
-            const float* g = src + ((size_t)co * cin + ci) * 9;
-            const int nb = co / 32, kg = ci / 16, lane = (co & 31) + 32 * ((ci & 15) >> 3), j = ci & 7;
-            for (int i = 0; i < 4; ++i)
-                for (int l = 0; l < 4; ++l) {
-                    double u = 0;
-                    for (int a = 0; a < 3; ++a)
-                        for (int b = 0; b < 3; ++b) u += G[i][a] * (double)g[a * 3 + b] * G[l][b];
-                    dst[((((size_t)(i * 4 + l) * KG + kg) * NB + nb) * 64 + lane) * 8 + j] = f16_rne((float)u);
-                }
-        }
-    return SBC_OK;
-}
-
-// ---- f16x2 forms (SBC_CONV_F16X2): two fp16 terms of w * 2^s + the scale trailer --------------------------------------
-// s: the power of two that puts the largest |w| of the layer into [2^13, 2^14) (fp16 keeps 11 significant bits down to
-// 2^-14, so every weight above 2^-27 of the largest one keeps its 22 bits); activations are scaled by 2^SBC_F16X2_ACT_SHIFT.
-static int f16x2_shift(const float* w, size_t n) {
-    float m = 0.f;
-    for (size_t i = 0; i < n; ++i) { const float a = fabsf(w[i]); if (a > m) m = a; }
-    if (!(m > 0.f) || !std::isfinite(m)) return 0;
-    int e = 0;
-    (void)frexpf(m, &e);                       // m = f * 2^e, f in [0.5, 1)
-    int s = 14 - e;
-    return s < -100 ? -100 : s > 100 ? 100 : s;
-}
-static inline void f16x2_terms(float w, int s, uint16_t* h, uint16_t* l) {
-    const float a = ldexpf(w, s);
-    const _Float16 hh = (_Float16)a;
-    const _Float16 ll = (_Float16)(a - (float)hh);
-    memcpy(h, &hh, 2);
-    memcpy(l, &ll, 2);
-}
-static void f16x2_trailer_write(uint16_t* dst, size_t n16, int s) {
-    // (act_scale, descale = 1 / (act_scale weight_scale), the weights' own descale 2^-s, 0): sbc_f16x2_calibrate rewrites the first two
-    const float tr[4] = {ldexpf(1.f, SBC_F16X2_ACT_SHIFT), ldexpf(1.f, -(s + SBC_F16X2_ACT_SHIFT)), ldexpf(1.f, -s), 0.f};
-    memcpy(dst + n16, tr, sizeof(tr));
-}
-
-// [cout][cin][taps] float32 -> the two-term fp16 fragment order (+ trailer); shared by the plain and the pooled packer
-static void pack_f16x2_taps(const float* src, int cout, int cin, int taps, uint16_t* dst) {
-    const int KG = cin / 16, NB = cout / 32;
-    const int s = f16x2_shift(src, (size_t)cout * cin * taps);
-    for (int tap = 0; tap < taps; ++tap)
-        for (int g = 0; g < KG; ++g)
-            for (int nb = 0; nb < NB; ++nb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int co = nb * 32 + (lane & 31), ci = g * 16 + 8 * (lane >> 5) + j;
-                        const size_t base = (((size_t)tap * KG + g) * NB + nb) * 2;
-                        f16x2_terms(src[((size_t)co * cin + ci) * taps + tap], s, &dst[((base + 0) * 64 + lane) * 8 + j],
-                                    &dst[((base + 1) * 64 + lane) * 8 + j]);
-                    }
-    f16x2_trailer_write(dst, (size_t)taps * KG * NB * 2 * 512, s);
-}
-
-int sbc_pack_conv_weight_f16x2(const float* src, int32_t cout, int32_t cin, int32_t ksize, uint16_t* dst) {
-    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_f16x2: NULL pointer");
-    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0 && (ksize == 1 || ksize == 3),
-                "sbc_pack_conv_weight_f16x2: cin %% 16, cout %% 32, ksize in {1,3} required (got %d, %d, %d)", cin, cout, ksize);
-    pack_f16x2_taps(src, cout, cin, ksize * ksize, dst);
-    return SBC_OK;
-}
-
-int sbc_pack_conv_weight_pooled_f16x2(const float* src, int32_t cout, int32_t cin, int32_t ksize, uint16_t* dst) {
-    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_pooled_f16x2: NULL pointer");
-    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0 && (ksize == 1 || ksize == 3),
-                "sbc_pack_conv_weight_pooled_f16x2: cin %% 16, cout %% 32, ksize in {1,3} required (got %d, %d, %d)", cin, cout, ksize);
-    // meanpool2(conv_k(x)) = conv_{k+1, stride 2}(x) with W'[p][q] = 1/4 sum_{a,b in {0,1}} W[p - a][q - b]   (layers.py:309-313)
-    const int k = ksize, k1 = ksize + 1;
+// meanpool2(conv_k(x)) = conv_{k+1, stride 2}(x) with W'[p][q] = 1/4 sum_{a,b in {0,1}} W[p - a][q - b]   (layers.py:309-313)
+std::vector<float> pooled_filter(const float* src, int cout, int cin, int k) {
+    const int k1 = k + 1;
     std::vector<float> wp((size_t)cout * cin * k1 * k1);
     for (size_t oc = 0; oc < (size_t)cout * cin; ++oc)
         for (int p = 0; p < k1; ++p)
@@ -870,40 +691,139 @@ int sbc_pack_conv_weight_pooled_f16x2(const float* src, int32_t cout, int32_t ci
                         if (p - a >= 0 && p - a < k && q - b >= 0 && q - b < k) v += (double)src[oc * k * k + (p - a) * k + (q - b)];
                 wp[oc * k1 * k1 + p * k1 + q] = (float)(0.25 * v);
             }
-    pack_f16x2_taps(wp.data(), cout, cin, k1 * k1, dst);
+    return wp;
+}
+
+// round-to-nearest-even fp32 -> bf16 (bit pattern), as v_cvt_pk_bf16_f32 does for finite values
+inline uint16_t bf16_rne(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    u += 0x7FFFu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+inline float bf16_to_f32(uint16_t b) {
+    const uint32_t u = (uint32_t)b << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+// round-to-nearest-even fp32 -> fp16 bit pattern (the host compiler's _Float16 conversion is IEEE RNE, like v_cvt_f16_f32)
+inline uint16_t f16_rne(float f) {
+    const _Float16 h = (_Float16)f;
+    uint16_t u;
+    memcpy(&u, &h, 2);
+    return u;
+}
+
+void pack_f32(const float* src, int cout, int cin, int taps, float* dst) {
+    pack_fragments<4, 1>(src, cout, cin, taps, dst, [](float w, float* t) { t[0] = w; });
+}
+void pack_bf16x3(const float* src, int cout, int cin, int taps, uint16_t* dst) {      // w = high + middle + low, each a bf16
+    pack_fragments<8, 3>(src, cout, cin, taps, dst, [](float w, uint16_t* t) {
+        t[0] = bf16_rne(w);
+        const float r1 = w - bf16_to_f32(t[0]);
+        t[1] = bf16_rne(r1);
+        t[2] = bf16_rne(r1 - bf16_to_f32(t[1]));
+    });
+}
+void pack_f16(const float* src, int cout, int cin, int taps, uint16_t* dst) {
+    pack_fragments<8, 1>(src, cout, cin, taps, dst, [](float w, uint16_t* t) { t[0] = f16_rne(w); });
+}
+
+// f16x2 (SBC_CONV_F16X2): two fp16 terms of w * 2^s + the scale trailer.
+// s: the power of two that puts the largest |w| of the layer into [2^13, 2^14) (fp16 keeps 11 significant bits down to
+// 2^-14, so every weight above 2^-27 of the largest one keeps its 22 bits); activations are scaled by 2^SBC_F16X2_ACT_SHIFT.
+int f16x2_shift(const float* w, size_t n) {
+    float m = 0.f;
+    for (size_t i = 0; i < n; ++i) { const float a = fabsf(w[i]); if (a > m) m = a; }
+    if (!(m > 0.f) || !std::isfinite(m)) return 0;
+    int e = 0;
+    (void)frexpf(m, &e);                       // m = f * 2^e, f in [0.5, 1)
+    int s = 14 - e;
+    return s < -100 ? -100 : s > 100 ? 100 : s;
+}
+void pack_f16x2(const float* src, int cout, int cin, int taps, uint16_t* dst) {
+    const int s = f16x2_shift(src, (size_t)cout * cin * taps);
+    pack_fragments<8, 2>(src, cout, cin, taps, dst, [s](float w, uint16_t* t) {
+        const float a = ldexpf(w, s);
+        const _Float16 h = (_Float16)a, l = (_Float16)(a - (float)h);
+        memcpy(&t[0], &h, 2);
+        memcpy(&t[1], &l, 2);
+    });
+    // (act_scale, descale = 1 / (act_scale weight_scale), the weights' own descale 2^-s, 0): sbc_f16x2_calibrate rewrites the first two
+    const float tr[4] = {ldexpf(1.f, SBC_F16X2_ACT_SHIFT), ldexpf(1.f, -(s + SBC_F16X2_ACT_SHIFT)), ldexpf(1.f, -s), 0.f};
+    memcpy(dst + (size_t)taps * cin * cout * 2, tr, sizeof(tr));
+}
+
+}  // namespace
+
+extern "C" {
+
+int sbc_pack_conv_weight(const float* src, int32_t cout, int32_t cin, int32_t ksize, float* dst) {
+    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight: NULL pointer");
+    SBC_REQUIRE(cin % 8 == 0 && cout % 32 == 0 && (ksize == 1 || ksize == 3),
+                "sbc_pack_conv_weight: cin %% 8, cout %% 32, ksize in {1,3} required (got %d, %d, %d)", cin, cout, ksize);
+    pack_f32(src, cout, cin, ksize * ksize, dst);
+    return SBC_OK;
+}
+
+int sbc_pack_conv_weight_winograd(const float* src, int32_t cout, int32_t cin, float* dst) {
+    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_winograd: NULL pointer");
+    SBC_REQUIRE(cin % 8 == 0 && cout % 32 == 0, "sbc_pack_conv_weight_winograd: cin %% 8, cout %% 32 required (got %d, %d)", cin, cout);
+    pack_f32(winograd_u(src, cout, cin).data(), cout, cin, 16, dst);
+    return SBC_OK;
+}
+
+int sbc_pack_conv_weight_split(const float* src, int32_t cout, int32_t cin, int32_t ksize, uint16_t* dst) {
+    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_split: NULL pointer");
+    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0 && (ksize == 1 || ksize == 3),
+                "sbc_pack_conv_weight_split: cin %% 16, cout %% 32, ksize in {1,3} required (got %d, %d, %d)", cin, cout, ksize);
+    pack_bf16x3(src, cout, cin, ksize * ksize, dst);
+    return SBC_OK;
+}
+
+int sbc_pack_conv_weight_winograd_split(const float* src, int32_t cout, int32_t cin, uint16_t* dst) {
+    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_winograd_split: NULL pointer");
+    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0, "sbc_pack_conv_weight_winograd_split: cin %% 16, cout %% 32 required (got %d, %d)", cin, cout);
+    pack_bf16x3(winograd_u(src, cout, cin).data(), cout, cin, 16, dst);
+    return SBC_OK;
+}
+
+int sbc_pack_conv_weight_f16(const float* src, int32_t cout, int32_t cin, int32_t ksize, uint16_t* dst) {
+    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_f16: NULL pointer");
+    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0 && (ksize == 1 || ksize == 3),
+                "sbc_pack_conv_weight_f16: cin %% 16, cout %% 32, ksize in {1,3} required (got %d, %d, %d)", cin, cout, ksize);
+    pack_f16(src, cout, cin, ksize * ksize, dst);
+    return SBC_OK;
+}
+
+int sbc_pack_conv_weight_winograd_f16(const float* src, int32_t cout, int32_t cin, uint16_t* dst) {
+    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_winograd_f16: NULL pointer");
+    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0, "sbc_pack_conv_weight_winograd_f16: cin %% 16, cout %% 32 required (got %d, %d)", cin, cout);
+    pack_f16(winograd_u(src, cout, cin).data(), cout, cin, 16, dst);
+    return SBC_OK;
+}
+
+int sbc_pack_conv_weight_f16x2(const float* src, int32_t cout, int32_t cin, int32_t ksize, uint16_t* dst) {
+    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_f16x2: NULL pointer");
+    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0 && (ksize == 1 || ksize == 3),
+                "sbc_pack_conv_weight_f16x2: cin %% 16, cout %% 32, ksize in {1,3} required (got %d, %d, %d)", cin, cout, ksize);
+    pack_f16x2(src, cout, cin, ksize * ksize, dst);
+    return SBC_OK;
+}
+
+int sbc_pack_conv_weight_pooled_f16x2(const float* src, int32_t cout, int32_t cin, int32_t ksize, uint16_t* dst) {
+    SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_pooled_f16x2: NULL pointer");
+    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0 && (ksize == 1 || ksize == 3),
+                "sbc_pack_conv_weight_pooled_f16x2: cin %% 16, cout %% 32, ksize in {1,3} required (got %d, %d, %d)", cin, cout, ksize);
+    pack_f16x2(pooled_filter(src, cout, cin, ksize).data(), cout, cin, (ksize + 1) * (ksize + 1), dst);
     return SBC_OK;
 }
 
 int sbc_pack_conv_weight_winograd_f16x2(const float* src, int32_t cout, int32_t cin, uint16_t* dst) {
     SBC_REQUIRE(src && dst, "sbc_pack_conv_weight_winograd_f16x2: NULL pointer");
-    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0, "sbc_pack_conv_weight_winograd_f16x2: cin %% 16, cout %% 32 required (got %d, %d)",
-                cin, cout);
-    static const double G[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-    std::vector<float> u((size_t)cout * cin * 16);             // torch-like [cout][cin][4][4]
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci) {
-            const float* g = src + ((size_t)co * cin + ci) * 9;
-            for (int i = 0; i < 4; ++i)
-                for (int l = 0; l < 4; ++l) {
-                    double v = 0;
-                    for (int j = 0; j < 3; ++j)
-                        for (int k = 0; k < 3; ++k) v += G[i][j] * (double)g[j * 3 + k] * G[l][k];
-                    u[((size_t)co * cin + ci) * 16 + i * 4 + l] = (float)v;
-                }
-        }
-    const int KG = cin / 16, NB = cout / 32;
-    const int s = f16x2_shift(u.data(), u.size());
-    for (int tap = 0; tap < 16; ++tap)
-        for (int g = 0; g < KG; ++g)
-            for (int nb = 0; nb < NB; ++nb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int co = nb * 32 + (lane & 31), ci = g * 16 + 8 * (lane >> 5) + j;
-                        const size_t base = (((size_t)tap * KG + g) * NB + nb) * 2;
-                        f16x2_terms(u[((size_t)co * cin + ci) * 16 + tap], s, &dst[((base + 0) * 64 + lane) * 8 + j],
-                                    &dst[((base + 1) * 64 + lane) * 8 + j]);
-                    }
-    f16x2_trailer_write(dst, (size_t)16 * KG * NB * 2 * 512, s);
+    SBC_REQUIRE(cin % 16 == 0 && cout % 32 == 0, "sbc_pack_conv_weight_winograd_f16x2: cin %% 16, cout %% 32 required (got %d, %d)", cin, cout);
+    pack_f16x2(winograd_u(src, cout, cin).data(), cout, cin, 16, dst);
     return SBC_OK;
 }
 

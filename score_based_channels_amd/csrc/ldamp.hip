@@ -18,12 +18,11 @@
 // read from its two sources) + 3 transposed convolutions (with their norm) + finish (1 x 1 convolution, unnorm, residual, divergence,
 // z update, NMSE) = 19 per unroll.
 #include "common.h"
+#include "host_params.h"
 #include "philox.h"
 #include <math.h>
 #include <string.h>
-#include <map>
 #include <string>
-#include <vector>
 
 namespace sbc {
 namespace {
@@ -536,8 +535,8 @@ void unet(const float* net, const Ws& ws, hipStream_t s) {
 }  // namespace sbc
 
 struct sbc_ldamp {
-    int n_nets = 0, device = 0;
-    float* wdev = nullptr;                              // [n_nets][NET_FLOATS]
+    int n_nets = 0;
+    sbc::ParamImage params;                             // [n_nets][NET_FLOATS]
 };
 
 extern "C" {
@@ -546,39 +545,31 @@ int sbc_ldamp_create(const sbc_tensor_ref* tensors, int32_t n_tensors, int32_t n
     using namespace sbc;
     SBC_REQUIRE(tensors && out && n_nets >= 1 && n_nets <= 64, "sbc_ldamp_create: need tensors, out and 1 <= n_nets <= 64 (got %d)", n_nets);
     SBC_REQUIRE(n_tensors == n_nets * N_TENSORS, "sbc_ldamp_create: %d nets have %d tensors (got %d)", n_nets, n_nets * N_TENSORS, n_tensors);
-    std::map<std::string, const sbc_tensor_ref*> sd;
-    for (int i = 0; i < n_tensors; ++i) {
-        SBC_REQUIRE(tensors[i].name && tensors[i].data, "sbc_ldamp_create: tensor %d has no name or data", i);
-        SBC_REQUIRE(sd.emplace(tensors[i].name, &tensors[i]).second, "sbc_ldamp_create: tensor %s given twice", tensors[i].name);
-    }
-    std::vector<float> host((size_t)n_nets * NET_FLOATS);
+    TensorIndex sd;
+    const char* twice = nullptr;
+    const int rc = sd.build("sbc_ldamp_create", tensors, n_tensors, &twice);
+    if (rc) return rc;
+    SBC_REQUIRE(!twice, "sbc_ldamp_create: tensor '%s' given twice", twice);
+    ParamImage params;
+    const size_t base = params.take((size_t)n_nets * NET_FLOATS);
     for (int u = 0; u < n_nets; ++u)
         for (int t = 0; t < N_TENSORS; ++t) {
-            const std::string name = "update_nets." + std::to_string(u) + "." + TENSORS[t].name;
-            auto it = sd.find(name);
-            SBC_REQUIRE(it != sd.end(), "sbc_ldamp_create: missing tensor %s", name.c_str());
-            SBC_REQUIRE(it->second->numel == TENSORS[t].numel, "sbc_ldamp_create: %s has %lld elements, expected %d", name.c_str(),
-                        (long long)it->second->numel, TENSORS[t].numel);
-            memcpy(host.data() + (size_t)u * NET_FLOATS + tensor_prefix(t), it->second->data, sizeof(float) * TENSORS[t].numel);
+            const float* w = sd.find("update_nets." + std::to_string(u) + "." + TENSORS[t].name, TENSORS[t].numel);
+            if (!w) return SBC_ERR_INVALID;
+            memcpy(params.host.data() + base + (size_t)u * NET_FLOATS + tensor_prefix(t), w, sizeof(float) * TENSORS[t].numel);
         }
+    const int rc_up = params.upload("sbc_ldamp_create");
+    if (rc_up) return rc_up;
     sbc_ldamp* h = new sbc_ldamp;
     h->n_nets = n_nets;
-    hipError_t e = hipGetDevice(&h->device);
-    if (e == hipSuccess) e = hipMalloc(&h->wdev, host.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->wdev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        set_error("sbc_ldamp_create: %s", hipGetErrorString(e));
-        if (h->wdev) (void)hipFree(h->wdev);
-        delete h;
-        return SBC_ERR_HIP;
-    }
+    h->params = params;
     *out = h;
     return SBC_OK;
 }
 
 void sbc_ldamp_destroy(sbc_ldamp* h) {
     if (!h) return;
-    if (h->wdev) (void)hipFree(h->wdev);
+    h->params.release();
     delete h;
 }
 
@@ -598,25 +589,17 @@ int sbc_ldamp_stage(int32_t stage, int32_t n_images, int64_t* offset, int32_t* c
     return SBC_OK;
 }
 
-static int ldamp_device_check(const sbc_ldamp* h, const char* who) {
-    using namespace sbc;
-    int dev = 0;
-    SBC_CHECK_HIP(hipGetDevice(&dev));
-    SBC_REQUIRE(dev == h->device, "%s: the handle lives on device %d, the current device is %d", who, h->device, dev);
-    return SBC_OK;
-}
-
 int sbc_ldamp_denoise(sbc_ldamp* h, int32_t net, const float* r, float* out, int32_t B, float* workspace, void* stream) {
     using namespace sbc;
     SBC_REQUIRE(h && r && out && workspace, "sbc_ldamp_denoise: NULL handle, r, out or workspace");
     SBC_REQUIRE(net >= 0 && net < h->n_nets, "sbc_ldamp_denoise: net %d out of range [0, %d)", net, h->n_nets);
     SBC_REQUIRE(B >= 0 && B <= 32768, "sbc_ldamp_denoise: B must be in [0, 32768] (got %d)", B);
-    int rc = ldamp_device_check(h, "sbc_ldamp_denoise");
+    const int rc = h->params.check_device("sbc_ldamp_denoise");
     if (rc) return rc;
     if (B == 0) return SBC_OK;
     hipStream_t s = (hipStream_t)stream;
     const Ws ws{workspace, B};
-    const float* wn = h->wdev + (size_t)net * NET_FLOATS;
+    const float* wn = h->params.dev + (size_t)net * NET_FLOATS;
     PrepArgs pa{};
     pa.r_in = r; pa.r = ws.at(S_R); pa.x = ws.at(S_X); pa.stat = ws.at(S_STAT); pa.B = B;
     hipLaunchKernelGGL(ldamp_prep_kernel, dim3(B), dim3(256), 0, s, pa);
@@ -640,7 +623,7 @@ int sbc_ldamp_run(sbc_ldamp* h, const sbc_ldamp_run_desc* d, void* stream) {
                                                                  {d->workspace, "workspace"}};
     for (const auto& q : need) SBC_REQUIRE(q.p, "sbc_ldamp_run: NULL %s", q.name);
     SBC_REQUIRE(!d->nmse || d->Htrue, "sbc_ldamp_run: nmse needs Htrue");
-    int rc = ldamp_device_check(h, "sbc_ldamp_run");
+    const int rc = h->params.check_device("sbc_ldamp_run");
     if (rc) return rc;
     if (d->B == 0) return SBC_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -656,7 +639,7 @@ int sbc_ldamp_run(sbc_ldamp* h, const sbc_ldamp_run_desc* d, void* stream) {
     }
     SBC_CHECK_HIP(hipMemcpyAsync(z, d->Y_herm, sizeof(float) * 2 * (size_t)B * Np * NR, hipMemcpyDeviceToDevice, s));
     for (int u = 0; u < U; ++u) {
-        const float* wn = h->wdev + (size_t)u * NET_FLOATS;
+        const float* wn = h->params.dev + (size_t)u * NET_FLOATS;
         const float* du = dirs + (size_t)u * B * 2 * PIX;
         PrepArgs pa{};
         pa.P = d->P_herm; pa.z = z; pa.h = u ? d->H_hat : nullptr; pa.eig = d->eig1; pa.dirs = du; pa.eps = eps;

@@ -8,10 +8,12 @@
 // record list with SBC_OP_LANGEVIN / SBC_OP_STEP_INC into a full annealed-Langevin step plan (sbc_plan_create).
 // tests/test_gpu_capi.py holds it to the Python host: identical records, bit-identical outputs.
 #include <string.h>
+#include <array>
 #include <map>
 #include <string>
 #include <vector>
 #include "common.h"
+#include "host_params.h"
 
 namespace {
 
@@ -33,6 +35,7 @@ struct POp {
     };
     std::vector<Block> blocks;               // SBC_OP_CHAIN: the RCU / CRP blocks in execution order (plan.py: Op.blocks)
     int lane = 0, signal = 0, wait0 = 0, wait1 = 0;   // launch lanes (sbc_op.lane / signal / wait; plan.hoist_skip_branches)
+    std::array<int, 5> inputs() const { return {src, stats, res1, res2, up}; }   // the tensors the record reads (-1: none)
     // the state_dict key that names the record's layer (plan.py: Op.name has the same prefix)
     const std::string& label() const { return !blocks.empty() ? blocks[0].w1 : !weight.empty() ? weight : norm_key; }
 };
@@ -247,7 +250,7 @@ struct sbc_score {
     std::vector<POp> pops;
     std::vector<size_t> slot_elems;
     std::vector<float*> slots;           // device, [B * slot_elems]
-    float* wdev = nullptr;               // all parameters, packed
+    sbc::ParamImage params;              // all parameters, packed
     float* sigmas = nullptr;             // device [num_classes]
     int64_t* labels = nullptr;           // device [B]
     sbc_endconv endc;
@@ -259,80 +262,12 @@ struct sbc_score {
 
 namespace {
 
-void assign_slots(sbc_score& s) {       // plan.assign_slots: linear scan, outputs never alias inputs of their own op
-    const int n_ops = (int)s.pops.size();
-    std::vector<int> last_use(s.tensors.size(), -1);
-    // a record on a lane is known to be complete at the first run-stream record that waits for an event its lane signals at or behind it
-    // (plan.assign_slots); without one, at the end of the list
-    std::vector<int> done_at(n_ops);
-    for (int i = 0; i < n_ops; ++i) {
-        done_at[i] = i;
-        if (!s.pops[i].lane) continue;
-        done_at[i] = n_ops - 1;
-        for (int k = i; k < n_ops && done_at[i] == n_ops - 1; ++k) {
-            if (s.pops[k].lane != s.pops[i].lane || !s.pops[k].signal) continue;
-            for (int m = k + 1; m < n_ops; ++m)
-                if (!s.pops[m].lane && (s.pops[m].wait0 == s.pops[k].signal || s.pops[m].wait1 == s.pops[k].signal)) { done_at[i] = m; break; }
-        }
-    }
-    for (int i = 0; i < n_ops; ++i)
-        for (int id : {s.pops[i].src, s.pops[i].stats, s.pops[i].res1, s.pops[i].res2, s.pops[i].up})
-            if (id >= 0 && done_at[i] > last_use[id]) last_use[id] = done_at[i];
-    std::map<size_t, std::vector<int>> free_slots;
-    std::vector<int> live;
-    auto elems = [&](int id) { return (size_t)s.tensors[id].h * s.tensors[id].w * s.tensors[id].c; };
-    auto pinned = [&](int id) { return id == s.x_t || id == s.out_t; };
-    auto alloc = [&](int id) {
-        auto& pool = free_slots[elems(id)];
-        if (!pool.empty() && !pinned(id)) { s.tensors[id].slot = pool.back(); pool.pop_back(); }
-        else { s.tensors[id].slot = (int)s.slot_elems.size(); s.slot_elems.push_back(elems(id)); }
-    };
-    alloc(s.x_t);
-    for (int i = 0; i < n_ops; ++i) {
-        const int dst = s.pops[i].dst, mom = s.pops[i].moments;
-        alloc(dst);
-        live.push_back(dst);
-        if (mom >= 0) { alloc(mom); live.push_back(mom); }
-        for (size_t k = 0; k < live.size();) {
-            const int id = live[k];
-            if (!pinned(id) && id != dst && id != mom && last_use[id] <= i) {
-                free_slots[elems(id)].push_back(s.tensors[id].slot);
-                live.erase(live.begin() + k);
-            } else {
-                ++k;
-            }
-        }
-    }
-}
+// ---- the steps of sbc_score_create, in the order they run -------------------------------------------------------------------
 
-float round_f16(float f) { return (float)(_Float16)f; }
-
-}  // namespace
-
-extern "C" {
-
-int sbc_score_create(const sbc_score_desc* d, const sbc_tensor_ref* tensors, int32_t n_tensors, sbc_score** out) {
-    SBC_REQUIRE(d && tensors && out && n_tensors > 0, "sbc_score_create: bad arguments");
-    SBC_REQUIRE(d->ngf == 32 && d->channels == 2, "sbc_score_create: kernels are instantiated for ngf = 32, 2 channels");
-    SBC_REQUIRE(d->nt > 0 && d->nr > 0 && d->nt % 8 == 0 && d->nr % 8 == 0,
-                "sbc_score_create: Nt and Nr must be multiples of 8 (three 2x mean pools), got %dx%d", d->nt, d->nr);
-    SBC_REQUIRE(d->batch > 0 && d->conv_mode >= 0 && d->conv_mode <= 3 && d->sigmas && d->num_classes > 0,
-                "sbc_score_create: batch, conv_mode in {0 bf16x3, 1 f32, 2 f16w, 3 f16x2}, sigmas required");
-    SBC_REQUIRE(!(d->flags & SBC_SCORE_FUSE_RES) || d->conv_mode == 3, "sbc_score_create: SBC_SCORE_FUSE_RES needs conv_mode 3 (f16x2)");
-    SBC_REQUIRE(!(d->flags & SBC_SCORE_FUSE_CHAIN) || d->conv_mode == 3, "sbc_score_create: SBC_SCORE_FUSE_CHAIN needs conv_mode 3 (f16x2)");
-    SBC_REQUIRE(!(d->flags & SBC_SCORE_FUSE_DOWN) || d->conv_mode == 3, "sbc_score_create: SBC_SCORE_FUSE_DOWN needs conv_mode 3 (f16x2)");
-    SBC_REQUIRE(!(d->flags & SBC_SCORE_FUSE_PAIRS) || d->conv_mode >= 2,
-                "sbc_score_create: SBC_SCORE_FUSE_PAIRS needs the fp16 weight forms (conv_mode 2 or 3)");
-    std::map<std::string, const sbc_tensor_ref*> sd;
-    for (int i = 0; i < n_tensors; ++i) {
-        SBC_REQUIRE(tensors[i].name && tensors[i].data, "sbc_score_create: tensor %d has no name / data", i);
-        sd[tensors[i].name] = &tensors[i];
-    }
-    sbc_score* s = new sbc_score();
-    s->desc = *d;
-    const int ngf = d->ngf, nt = d->nt, nr = d->nr, B = d->batch;
-    // ---- wiring (plan.build_score_plan)
-    Builder b{ngf, nt, nr};
+// 1. wiring (plan.build_score_plan, plan.merge_chains, plan.TAG_DIRECT_MID)
+void wire(Builder& b, sbc_score& s) {
+    const sbc_score_desc* d = &s.desc;
+    const int ngf = d->ngf, nt = d->nt, nr = d->nr;
     b.fuse_pairs = (d->flags & SBC_SCORE_FUSE_PAIRS) != 0;
     b.f16w = d->conv_mode == 2;
     b.fuse_res = (d->flags & SBC_SCORE_FUSE_RES) != 0;
@@ -371,7 +306,7 @@ int sbc_score_create(const sbc_score_desc* d, const sbc_tensor_ref* tensors, int
         const POp& c = b.ops[k + 1];
         bool ok = a.kind == SBC_OP_CHAIN && c.kind == SBC_OP_CHAIN && c.src == a.dst && a.blocks.size() + c.blocks.size() <= SBC_CHAIN_MAX_BLOCKS;
         for (size_t j = k + 2; ok && j < b.ops.size(); ++j)
-            for (int id : {b.ops[j].src, b.ops[j].stats, b.ops[j].res1, b.ops[j].res2, b.ops[j].up}) ok = ok && id != a.dst;
+            for (int id : b.ops[j].inputs()) ok = ok && id != a.dst;
         if (ok) {
             a.blocks.insert(a.blocks.end(), c.blocks.begin(), c.blocks.end());
             a.dst = c.dst;
@@ -382,93 +317,118 @@ int sbc_score_create(const sbc_score_desc* d, const sbc_tensor_ref* tensors, int
     }
     for (auto& o : b.ops)                   // plan.TAG_DIRECT_MID
         if (o.tag == 3 && !(o.flags & (SBC_PRO_NORM | SBC_EPI_UP | SBC_EPI_MOMENTS_OUT))) o.tag = 5;
-    if (d->flags & SBC_SCORE_SKIP_LANES) {
-        // plan.hoist_skip_branches with plan.DEFAULT_SKIP_SPEC: the decoder's skip branches behind their anchors, on lane 1
-        static const char* const spec[5][2] = {{"refine5.adapt_convs.0.", "res3.1."}, {"refine4.adapt_convs.0.", "res3.1."}, {"refine3.adapt_convs.0.", "res3.1."},
-                                               {"refine31.adapt_convs.0.", "res31.1."}, {"refine2.adapt_convs.0.", "res4.1."}};
-        auto starts = [](const std::string& v, const char* pre) { return v.compare(0, strlen(pre), pre) == 0; };
-        int next_evt = 1;
-        auto signal_of = [&](POp& o) { if (!o.signal) o.signal = next_evt++; return o.signal; };
-        for (const auto& e : spec) {
-            int i0 = -1, i1 = -1;
-            for (int i = 0; i < (int)b.ops.size(); ++i)
-                if (starts(b.ops[i].label(), e[0])) { if (i0 < 0) i0 = i; i1 = i; }
-            if (i0 < 0) continue;                                   // (a plan without this branch as records of its own)
-            for (int i = i0; i <= i1; ++i) SBC_REQUIRE(starts(b.ops[i].label(), e[0]) && !b.ops[i].lane, "sbc_score_create: skip branch %s is not one run of records", e[0]);
-            int a = -1;
-            for (int i = 0; i < i0; ++i) if (starts(b.ops[i].label(), e[1])) a = i;
-            SBC_REQUIRE(a >= 0, "sbc_score_create: anchor %s of skip branch %s not found", e[1], e[0]);
-            std::vector<POp> branch(b.ops.begin() + i0, b.ops.begin() + i1 + 1);
-            const int result = branch.back().dst;
-            b.ops.erase(b.ops.begin() + i0, b.ops.begin() + i1 + 1);
-            int consumer = -1;
-            for (int i = i0; i < (int)b.ops.size() && consumer < 0; ++i)
-                for (int id : {b.ops[i].src, b.ops[i].stats, b.ops[i].res1, b.ops[i].res2, b.ops[i].up}) if (id == result) consumer = i;
-            SBC_REQUIRE(consumer >= 0 && !b.ops[consumer].wait1, "sbc_score_create: skip branch %s has no consumer with a free wait slot", e[0]);
-            for (auto& o : branch) o.lane = 1;
-            branch.front().wait0 = signal_of(b.ops[a]);
-            const int done = signal_of(branch.back());
-            (b.ops[consumer].wait0 ? b.ops[consumer].wait1 : b.ops[consumer].wait0) = done;
-            b.ops.insert(b.ops.begin() + a + 1, branch.begin(), branch.end());
+    s.x_t = x; s.out_t = o_t;
+}
+
+// 2. SBC_SCORE_SKIP_LANES: plan.hoist_skip_branches with plan.DEFAULT_SKIP_SPEC, the decoder's skip branches behind their anchors, on lane 1
+int hoist_lanes(Builder& b) {
+    static const char* const spec[5][2] = {{"refine5.adapt_convs.0.", "res3.1."}, {"refine4.adapt_convs.0.", "res3.1."}, {"refine3.adapt_convs.0.", "res3.1."},
+                                           {"refine31.adapt_convs.0.", "res31.1."}, {"refine2.adapt_convs.0.", "res4.1."}};
+    auto starts = [](const std::string& v, const char* pre) { return v.compare(0, strlen(pre), pre) == 0; };
+    int next_evt = 1;
+    auto signal_of = [&](POp& o) { if (!o.signal) o.signal = next_evt++; return o.signal; };
+    for (const auto& e : spec) {
+        int i0 = -1, i1 = -1;
+        for (int i = 0; i < (int)b.ops.size(); ++i)
+            if (starts(b.ops[i].label(), e[0])) { if (i0 < 0) i0 = i; i1 = i; }
+        if (i0 < 0) continue;                                   // (a plan without this branch as records of its own)
+        for (int i = i0; i <= i1; ++i) SBC_REQUIRE(starts(b.ops[i].label(), e[0]) && !b.ops[i].lane, "sbc_score_create: skip branch %s is not one run of records", e[0]);
+        int a = -1;
+        for (int i = 0; i < i0; ++i) if (starts(b.ops[i].label(), e[1])) a = i;
+        SBC_REQUIRE(a >= 0, "sbc_score_create: anchor %s of skip branch %s not found", e[1], e[0]);
+        std::vector<POp> branch(b.ops.begin() + i0, b.ops.begin() + i1 + 1);
+        const int result = branch.back().dst;
+        b.ops.erase(b.ops.begin() + i0, b.ops.begin() + i1 + 1);
+        int consumer = -1;
+        for (int i = i0; i < (int)b.ops.size() && consumer < 0; ++i)
+            for (int id : b.ops[i].inputs()) if (id == result) consumer = i;
+        SBC_REQUIRE(consumer >= 0 && !b.ops[consumer].wait1, "sbc_score_create: skip branch %s has no consumer with a free wait slot", e[0]);
+        for (auto& o : branch) o.lane = 1;
+        branch.front().wait0 = signal_of(b.ops[a]);
+        const int done = signal_of(branch.back());
+        (b.ops[consumer].wait0 ? b.ops[consumer].wait1 : b.ops[consumer].wait0) = done;
+        b.ops.insert(b.ops.begin() + a + 1, branch.begin(), branch.end());
+    }
+    return SBC_OK;
+}
+
+// 3. plan.assign_slots: linear scan, outputs never alias inputs of their own op
+void assign_slots(sbc_score& s) {
+    const int n_ops = (int)s.pops.size();
+    std::vector<int> last_use(s.tensors.size(), -1);
+    // a record on a lane is known to be complete at the first run-stream record that waits for an event its lane signals at or behind it
+    // (plan.assign_slots); without one, at the end of the list
+    std::vector<int> done_at(n_ops);
+    for (int i = 0; i < n_ops; ++i) {
+        done_at[i] = i;
+        if (!s.pops[i].lane) continue;
+        done_at[i] = n_ops - 1;
+        for (int k = i; k < n_ops && done_at[i] == n_ops - 1; ++k) {
+            if (s.pops[k].lane != s.pops[i].lane || !s.pops[k].signal) continue;
+            for (int m = k + 1; m < n_ops; ++m)
+                if (!s.pops[m].lane && (s.pops[m].wait0 == s.pops[k].signal || s.pops[m].wait1 == s.pops[k].signal)) { done_at[i] = m; break; }
         }
     }
-    s->tensors = b.t; s->pops = b.ops; s->x_t = x; s->out_t = o_t;
-    assign_slots(*s);
-
-    // ---- parameters: one flat host image (16-byte aligned entries), packed by the library's own packers
-    const bool f16w = d->conv_mode == 2, f16x2 = d->conv_mode == 3;
-    std::vector<float> host;
-    std::map<std::string, size_t> off;
-    auto reserve = [&](const std::string& key, size_t n) {
-        host.resize((host.size() + 3) / 4 * 4);
-        off[key] = host.size();
-        host.resize(host.size() + n);
-        return host.data() + off[key];
+    for (int i = 0; i < n_ops; ++i)
+        for (int id : s.pops[i].inputs())
+            if (id >= 0 && done_at[i] > last_use[id]) last_use[id] = done_at[i];
+    std::map<size_t, std::vector<int>> free_slots;
+    std::vector<int> live;
+    auto elems = [&](int id) { return (size_t)s.tensors[id].h * s.tensors[id].w * s.tensors[id].c; };
+    auto pinned = [&](int id) { return id == s.x_t || id == s.out_t; };
+    auto alloc = [&](int id) {
+        auto& pool = free_slots[elems(id)];
+        if (!pool.empty() && !pinned(id)) { s.tensors[id].slot = pool.back(); pool.pop_back(); }
+        else { s.tensors[id].slot = (int)s.slot_elems.size(); s.slot_elems.push_back(elems(id)); }
     };
-    auto find = [&](const std::string& key, int64_t numel) -> const float* {
-        auto it = sd.find(key);
-        if (it == sd.end()) { set_error("sbc_score_create: tensor '%s' missing from the state dict", key.c_str()); return nullptr; }
-        if (it->second->numel != numel) {
-            set_error("sbc_score_create: tensor '%s' has %lld elements, expected %lld", key.c_str(),
-                      (long long)it->second->numel, (long long)numel);
-            return nullptr;
+    alloc(s.x_t);
+    for (int i = 0; i < n_ops; ++i) {
+        const int dst = s.pops[i].dst, mom = s.pops[i].moments;
+        alloc(dst);
+        live.push_back(dst);
+        if (mom >= 0) { alloc(mom); live.push_back(mom); }
+        for (size_t k = 0; k < live.size();) {
+            const int id = live[k];
+            if (!pinned(id) && id != dst && id != mom && last_use[id] <= i) {
+                free_slots[elems(id)].push_back(s.tensors[id].slot);
+                live.erase(live.begin() + k);
+            } else {
+                ++k;
+            }
         }
-        return it->second->data;
-    };
-    auto fail = [&]() { sbc_score_destroy(s); return SBC_ERR_INVALID; };
+    }
+}
+
+// 4. parameters: one flat host image (16-byte aligned entries), packed by the library's own packers
+int pack_params(sbc_score& s, const sbc::TensorIndex& sd) {
+    const int conv_mode = s.desc.conv_mode;
+    const bool f16w = conv_mode == 2, f16x2 = conv_mode == 3;
+    sbc::ParamImage& im = s.params;
     std::vector<float> tmp;
     auto rounded = [&](const float* p, size_t n) {      // fp16 parameters for conv_mode f16w (module.half() semantics)
         if (!f16w) return p;
         tmp.assign(p, p + n);
-        for (auto& v : tmp) v = round_f16(v);
+        for (auto& v : tmp) v = (float)(_Float16)v;
         return (const float*)tmp.data();
     };
-    for (const POp& o : s->pops) {
-        const Tn& src = s->tensors[o.geom >= 0 ? o.geom : o.src];
-        const Tn& dst = s->tensors[o.dst];
-        const std::string& nkey = o.kind == SBC_OP_INORM_STATS ? o.weight : o.kind == SBC_OP_RES_BLOCK ? o.norm2 : o.norm_key;
-        if (!nkey.empty() && !off.count(nkey)) {             // a norm's (alpha | gamma | beta), [3][C]
-            for (int k = 0; k < 3; ++k) {
-                const char* suffix[3] = {".alpha", ".gamma", ".beta"};
-                const float* v = find(nkey + suffix[k], src.c);
-                if (!v) return fail();
-                if (k == 0) reserve(nkey, 3 * (size_t)src.c);
-                v = rounded(v, src.c);
-                memcpy(host.data() + off[nkey] + (size_t)k * src.c, v, sizeof(float) * src.c);
-            }
+    auto norm = [&](const std::string& nkey, int c) {   // a norm's (alpha | gamma | beta), [3][C]; false: a tensor is missing
+        if (nkey.empty() || im.has(nkey)) return true;
+        for (int k = 0; k < 3; ++k) {
+            const char* suffix[3] = {".alpha", ".gamma", ".beta"};
+            const float* v = sd.find(nkey + suffix[k], c);
+            if (!v) return false;
+            if (k == 0) im.reserve(nkey, 3 * (size_t)c);
+            memcpy(im.at(nkey) + (size_t)k * c, rounded(v, c), sizeof(float) * c);
         }
+        return true;
+    };
+    auto u16 = [&](const std::string& key, size_t n_floats) { return (uint16_t*)im.reserve(key, n_floats); };
+    for (const POp& o : s.pops) {
+        const Tn& src = s.tensors[o.geom >= 0 ? o.geom : o.src];
+        const Tn& dst = s.tensors[o.dst];
+        if (!norm(o.kind == SBC_OP_INORM_STATS ? o.weight : o.kind == SBC_OP_RES_BLOCK ? o.norm2 : o.norm_key, src.c)) return SBC_ERR_INVALID;
         for (const auto& bl : o.blocks)                      // the norms of the RES blocks of a CHAIN record
-            for (const std::string& nk : {bl.norm1, bl.norm2}) {
-                if (nk.empty() || off.count(nk)) continue;
-                for (int k = 0; k < 3; ++k) {
-                    const char* suffix[3] = {".alpha", ".gamma", ".beta"};
-                    const float* v = find(nk + suffix[k], src.c);
-                    if (!v) return fail();
-                    if (k == 0) reserve(nk, 3 * (size_t)src.c);
-                    v = rounded(v, src.c);
-                    memcpy(host.data() + off[nk] + (size_t)k * src.c, v, sizeof(float) * src.c);
-                }
-            }
+            if (!norm(bl.norm1, src.c) || !norm(bl.norm2, src.c)) return SBC_ERR_INVALID;
         if (o.kind == SBC_OP_INORM_STATS) continue;
         if (o.weight.empty() && o.blocks.empty()) continue;   // max pooling has no parameters
         const int k = o.ksize, cin = src.c, cout = dst.c;
@@ -476,89 +436,93 @@ int sbc_score_create(const sbc_score_desc* d, const sbc_tensor_ref* tensors, int
         std::vector<std::string> wkeys{o.weight, o.weight2};
         for (const auto& bl : o.blocks) { wkeys.push_back(bl.w1); wkeys.push_back(bl.w2); wkeys.push_back(bl.w3); }
         for (const std::string& wkey : wkeys) {
-        if (wkey.empty()) continue;
-        if (o.kind == SBC_OP_CONV_DOWN) {
-            // the pooled stride-2 filters: 3x3 -> 4x4 (conv2), 1x1 -> 2x2 (shortcut)   (scorenet.load_state_dict: '#pool')
-            if (off.count(wkey + "#pool")) continue;
-            const int kk = wkey == o.weight2 ? 1 : 3;
-            const float* w2 = find(wkey, (int64_t)cout * cin * kk * kk);
-            if (!w2) return fail();
-            sbc_pack_conv_weight_pooled_f16x2(w2, cout, cin, kk, (uint16_t*)reserve(wkey + "#pool", sbc_f16x2_elems((kk + 1) * (kk + 1), cin, cout) / 2));
-            continue;
-        }
-        if (!off.count(wkey) && !off.count(wkey + "#split")) {
-            const float* w = find(wkey, (int64_t)wn);
-            if (!w) return fail();
+            if (wkey.empty()) continue;
+            if (o.kind == SBC_OP_CONV_DOWN) {
+                // the pooled stride-2 filters: 3x3 -> 4x4 (conv2), 1x1 -> 2x2 (shortcut)   (scorenet.load_state_dict: '#pool')
+                if (im.has(wkey + "#pool")) continue;
+                const int kk = wkey == o.weight2 ? 1 : 3;
+                const float* w2 = sd.find(wkey, (int64_t)cout * cin * kk * kk);
+                if (!w2) return SBC_ERR_INVALID;
+                sbc_pack_conv_weight_pooled_f16x2(w2, cout, cin, kk, u16(wkey + "#pool", sbc_f16x2_elems((kk + 1) * (kk + 1), cin, cout) / 2));
+                continue;
+            }
+            if (im.has(wkey) || im.has(wkey + "#split")) continue;
+            const float* w = sd.find(wkey, (int64_t)wn);
+            if (!w) return SBC_ERR_INVALID;
             w = rounded(w, wn);
-            std::vector<float> wkeep(w, w + wn);          // `tmp` is reused below
-            const std::string& okey = wkey;
+            const std::vector<float> wkeep(w, w + wn);
             if (o.kind == SBC_OP_CONV_PAIR || o.kind == SBC_OP_CONV_POOL || o.kind == SBC_OP_RES_BLOCK || o.kind == SBC_OP_CHAIN) {
                 // the fused kernels read the direct fp16 forms only
-                if (f16x2) sbc_pack_conv_weight_f16x2(wkeep.data(), cout, cin, k, (uint16_t*)reserve(okey + "#split", sbc_f16x2_elems(k * k, cin, cout) / 2));
-                else sbc_pack_conv_weight_f16(wkeep.data(), cout, cin, k, (uint16_t*)reserve(okey + "#split", (wn + 1) / 2));
+                if (f16x2) sbc_pack_conv_weight_f16x2(wkeep.data(), cout, cin, k, u16(wkey + "#split", sbc_f16x2_elems(k * k, cin, cout) / 2));
+                else sbc_pack_conv_weight_f16(wkeep.data(), cout, cin, k, u16(wkey + "#split", (wn + 1) / 2));
             } else if (o.kind != SBC_OP_CONV) {
-                memcpy(reserve(o.weight, wn), wkeep.data(), sizeof(float) * wn);
-            } else if (d->conv_mode == 1) {
-                sbc_pack_conv_weight(wkeep.data(), cout, cin, k, reserve(o.weight, wn));
-                if (k == 3) sbc_pack_conv_weight_winograd(wkeep.data(), cout, cin, reserve(o.weight + "#winograd", (size_t)cout * cin * 16));
-            } else if (d->conv_mode == 0) {
-                sbc_pack_conv_weight_split(wkeep.data(), cout, cin, k, (uint16_t*)reserve(o.weight + "#split", wn * 3 / 2));
-                if (k == 3) sbc_pack_conv_weight_winograd_split(wkeep.data(), cout, cin,
-                                                               (uint16_t*)reserve(o.weight + "#winograd_split", (size_t)cout * cin * 16 * 3 / 2));
+                memcpy(im.reserve(o.weight, wn), wkeep.data(), sizeof(float) * wn);
+            } else if (conv_mode == 1) {
+                sbc_pack_conv_weight(wkeep.data(), cout, cin, k, im.reserve(o.weight, wn));
+                if (k == 3) sbc_pack_conv_weight_winograd(wkeep.data(), cout, cin, im.reserve(o.weight + "#winograd", (size_t)cout * cin * 16));
+            } else if (conv_mode == 0) {
+                sbc_pack_conv_weight_split(wkeep.data(), cout, cin, k, u16(o.weight + "#split", wn * 3 / 2));
+                if (k == 3) sbc_pack_conv_weight_winograd_split(wkeep.data(), cout, cin, u16(o.weight + "#winograd_split", (size_t)cout * cin * 16 * 3 / 2));
             } else if (f16x2) {
-                sbc_pack_conv_weight_f16x2(wkeep.data(), cout, cin, k, (uint16_t*)reserve(o.weight + "#split", sbc_f16x2_elems(k * k, cin, cout) / 2));
-                if (k == 3) sbc_pack_conv_weight_winograd_f16x2(wkeep.data(), cout, cin,
-                                                               (uint16_t*)reserve(o.weight + "#winograd_split", sbc_f16x2_elems(16, cin, cout) / 2));
+                sbc_pack_conv_weight_f16x2(wkeep.data(), cout, cin, k, u16(o.weight + "#split", sbc_f16x2_elems(k * k, cin, cout) / 2));
+                if (k == 3) sbc_pack_conv_weight_winograd_f16x2(wkeep.data(), cout, cin, u16(o.weight + "#winograd_split", sbc_f16x2_elems(16, cin, cout) / 2));
             } else {
-                sbc_pack_conv_weight_f16(wkeep.data(), cout, cin, k, (uint16_t*)reserve(o.weight + "#split", (wn + 1) / 2));
-                if (k == 3) sbc_pack_conv_weight_winograd_f16(wkeep.data(), cout, cin,
-                                                             (uint16_t*)reserve(o.weight + "#winograd_split", (size_t)cout * cin * 16 / 2));
+                sbc_pack_conv_weight_f16(wkeep.data(), cout, cin, k, u16(o.weight + "#split", (wn + 1) / 2));
+                if (k == 3) sbc_pack_conv_weight_winograd_f16(wkeep.data(), cout, cin, u16(o.weight + "#winograd_split", (size_t)cout * cin * 16 / 2));
             }
-        }
         }
         std::vector<std::string> bkeys{o.bias, o.bias2};
         for (const auto& bl : o.blocks) { bkeys.push_back(bl.bias1); bkeys.push_back(bl.bias2); bkeys.push_back(bl.bias3); }
         for (const std::string& bkey : bkeys) {
-            if (bkey.empty() || off.count(bkey)) continue;
-            const float* bv = find(bkey, cout);
-            if (!bv) return fail();
-            bv = rounded(bv, cout);
-            memcpy(reserve(bkey, cout), bv, sizeof(float) * cout);
+            if (bkey.empty() || im.has(bkey)) continue;
+            const float* bv = sd.find(bkey, cout);
+            if (!bv) return SBC_ERR_INVALID;
+            memcpy(im.reserve(bkey, cout), rounded(bv, cout), sizeof(float) * cout);
         }
     }
-    // ---- device memory
-    auto hip_fail = [&](hipError_t e, const char* what) {
-        set_error("sbc_score_create: %s failed: %s", what, hipGetErrorString(e));
-        sbc_score_destroy(s);
+    return SBC_OK;
+}
+
+// 5. device memory: the parameter image, the noise levels, the labels, one buffer per activation slot
+int allocate(sbc_score& s) {
+    const sbc_score_desc& d = s.desc;
+    int rc = s.params.upload("sbc_score_create");
+    if (rc) return rc;
+    hipError_t e;
+    auto hip_fail = [&](const char* what) {
+        sbc::set_error("sbc_score_create: %s failed: %s", what, hipGetErrorString(e));
         return SBC_ERR_HIP;
     };
-    hipError_t e;
-    if ((e = hipMalloc((void**)&s->wdev, host.size() * sizeof(float))) != hipSuccess) return hip_fail(e, "hipMalloc(weights)");
-    if ((e = hipMemcpy(s->wdev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return hip_fail(e, "hipMemcpy(weights)");
-    if ((e = hipMalloc((void**)&s->sigmas, d->num_classes * sizeof(float))) != hipSuccess) return hip_fail(e, "hipMalloc(sigmas)");
-    if ((e = hipMemcpy(s->sigmas, d->sigmas, d->num_classes * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return hip_fail(e, "hipMemcpy(sigmas)");
-    if ((e = hipMalloc((void**)&s->labels, B * sizeof(int64_t))) != hipSuccess) return hip_fail(e, "hipMalloc(labels)");
-    if ((e = hipMemset(s->labels, 0, B * sizeof(int64_t))) != hipSuccess) return hip_fail(e, "hipMemset(labels)");
-    s->slots.assign(s->slot_elems.size(), nullptr);
-    for (size_t i = 0; i < s->slot_elems.size(); ++i)
-        if ((e = hipMalloc((void**)&s->slots[i], (size_t)B * s->slot_elems[i] * sizeof(float))) != hipSuccess)
-            return hip_fail(e, "hipMalloc(activation slot)");
-    s->endc.sigmas = s->sigmas; s->endc.labels = s->labels; s->endc.sigma_of_step = nullptr; s->endc.step = nullptr;
-    // ---- records (scorenet.ScoreNet.bind)
+    if ((e = hipMalloc((void**)&s.sigmas, d.num_classes * sizeof(float))) != hipSuccess) return hip_fail("hipMalloc(sigmas)");
+    if ((e = hipMemcpy(s.sigmas, d.sigmas, d.num_classes * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return hip_fail("hipMemcpy(sigmas)");
+    if ((e = hipMalloc((void**)&s.labels, d.batch * sizeof(int64_t))) != hipSuccess) return hip_fail("hipMalloc(labels)");
+    if ((e = hipMemset(s.labels, 0, d.batch * sizeof(int64_t))) != hipSuccess) return hip_fail("hipMemset(labels)");
+    s.slots.assign(s.slot_elems.size(), nullptr);
+    for (size_t i = 0; i < s.slot_elems.size(); ++i)
+        if ((e = hipMalloc((void**)&s.slots[i], (size_t)d.batch * s.slot_elems[i] * sizeof(float))) != hipSuccess)
+            return hip_fail("hipMalloc(activation slot)");
+    s.endc.sigmas = s.sigmas; s.endc.labels = s.labels; s.endc.sigma_of_step = nullptr; s.endc.step = nullptr;
+    return SBC_OK;
+}
+
+// 6. records (scorenet.ScoreNet.bind) and the plan that runs them
+int bind_records(sbc_score& s) {
+    const int conv_mode = s.desc.conv_mode;
+    const bool f16w = conv_mode == 2, f16x2 = conv_mode == 3;
     size_t n_chains = 0;
-    for (const POp& o : s->pops) n_chains += o.kind == SBC_OP_CHAIN;
-    s->chains.reserve(n_chains);
-    for (const POp& o : s->pops) {
+    for (const POp& o : s.pops) n_chains += o.kind == SBC_OP_CHAIN;
+    s.chains.reserve(n_chains);
+    auto wp = [&](const std::string& key) -> const void* { return s.params.dev_at(key); };
+    for (const POp& o : s.pops) {
         sbc_op r;
         memset(&r, 0, sizeof(r));
-        const Tn& src = s->tensors[o.geom >= 0 ? o.geom : o.src];     // (statistics from tile moments: the image's dims)
-        const Tn& dst = s->tensors[o.dst];
-        r.kind = o.kind; r.flags = o.flags; r.B = B; r.H = src.h; r.W = src.w;
+        const Tn& src = s.tensors[o.geom >= 0 ? o.geom : o.src];     // (statistics from tile moments: the image's dims)
+        const Tn& dst = s.tensors[o.dst];
+        r.kind = o.kind; r.flags = o.flags; r.B = s.desc.batch; r.H = src.h; r.W = src.w;
         r.cin = src.c; r.cout = dst.c; r.ksize = o.ksize; r.dil = o.dil; r.tag = o.tag;
         r.lane = o.lane; r.signal = o.signal; r.wait[0] = o.wait0; r.wait[1] = o.wait1;
-        r.in = s->slots[s->tensors[o.src].slot]; r.out = s->slots[dst.slot];
-        if (o.moments >= 0) r.aux = s->slots[s->tensors[o.moments].slot];
-        auto wp = [&](const std::string& key) -> const void* { return off.count(key) ? s->wdev + off[key] : nullptr; };
+        r.in = s.slots[s.tensors[o.src].slot]; r.out = s.slots[dst.slot];
+        if (o.moments >= 0) r.aux = s.slots[s.tensors[o.moments].slot];
         if (o.kind == SBC_OP_CONV_PAIR) {
             r.weight_split = wp(o.weight + "#split");
             r.weight2_split = wp(o.weight2 + "#split");
@@ -589,8 +553,8 @@ int sbc_score_create(const sbc_score_desc* d, const sbc_tensor_ref* tensors, int
                     if (!bl.w3.empty()) { ch.w3[k] = wp(bl.w3 + "#split"); ch.bias3[k] = (const float*)wp(bl.bias3); }
                 }
             }
-            s->chains.push_back(ch);
-            r.ext = &s->chains.back();
+            s.chains.push_back(ch);
+            r.ext = &s.chains.back();
             r.flags |= SBC_CONV_F16X2;
         } else if (o.kind == SBC_OP_RES_BLOCK) {
             r.weight_split = wp(o.weight + "#split");
@@ -601,7 +565,7 @@ int sbc_score_create(const sbc_score_desc* d, const sbc_tensor_ref* tensors, int
             r.flags |= SBC_CONV_F16X2;
         } else if (o.kind != SBC_OP_CONV) {
             r.weight = wp(o.weight);
-        } else if (d->conv_mode == 1) {
+        } else if (conv_mode == 1) {
             r.weight = wp(o.weight);
             if (o.ksize == 3 && o.dil == 1) r.weight_wino = wp(o.weight + "#winograd");
         } else {
@@ -610,30 +574,68 @@ int sbc_score_create(const sbc_score_desc* d, const sbc_tensor_ref* tensors, int
             if (f16w) r.flags |= SBC_CONV_F16W;
             if (f16x2) r.flags |= SBC_CONV_F16X2;
         }
-        if ((d->conv_mode == 0 || d->conv_mode == 1) && o.kind == SBC_OP_CONV && (o.flags & SBC_PRO_ELU)) r.flags |= SBC_PRO_ELU_ACC;   // scorenet.bind
+        if ((conv_mode == 0 || conv_mode == 1) && o.kind == SBC_OP_CONV && (o.flags & SBC_PRO_ELU)) r.flags |= SBC_PRO_ELU_ACC;   // scorenet.bind
         if (!o.bias.empty()) r.bias = wp(o.bias);
-        if (o.stats >= 0) r.stats = s->slots[s->tensors[o.stats].slot];
+        if (o.stats >= 0) r.stats = s.slots[s.tensors[o.stats].slot];
         if (!o.norm_key.empty()) r.stats = wp(o.norm_key);
-        if (o.res1 >= 0) r.res1 = s->slots[s->tensors[o.res1].slot];
-        if (o.res2 >= 0) r.res2 = s->slots[s->tensors[o.res2].slot];
-        if (o.up >= 0) { r.up = s->slots[s->tensors[o.up].slot]; r.up_h = s->tensors[o.up].h; r.up_w = s->tensors[o.up].w; }
-        if (o.kind == SBC_OP_END_CONV) r.ext = &s->endc;
-        s->ops.push_back(r);
+        if (o.res1 >= 0) r.res1 = s.slots[s.tensors[o.res1].slot];
+        if (o.res2 >= 0) r.res2 = s.slots[s.tensors[o.res2].slot];
+        if (o.up >= 0) { r.up = s.slots[s.tensors[o.up].slot]; r.up_h = s.tensors[o.up].h; r.up_w = s.tensors[o.up].w; }
+        if (o.kind == SBC_OP_END_CONV) r.ext = &s.endc;
+        s.ops.push_back(r);
     }
-    const int rc = sbc_plan_create(s->ops.data(), (int32_t)s->ops.size(), &s->plan);
-    if (rc) { sbc_score_destroy(s); return rc; }
-    if (f16x2) {
-        // per-layer activation scales (include/sbc_hip.h: sbc_f16x2_calibrate; scorenet.ScoreNet._ensure_calibrated): one pass over
-        // the fixed calibration input in the first sample of the x buffer
-        const size_t n = (size_t)nt * nr * d->channels;
-        std::vector<float> pat(n);
-        int rc2 = sbc_f16x2_calibration_input(pat.data(), (int64_t)n);
-        if (!rc2 && hipMemcpy(s->slots[s->tensors[s->x_t].slot], pat.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("sbc_score_create: upload of the calibration input failed");
-            rc2 = SBC_ERR_HIP;
-        }
-        if (!rc2) rc2 = sbc_f16x2_calibrate(s->ops.data(), (int32_t)s->ops.size(), nullptr);
-        if (rc2) { sbc_score_destroy(s); return rc2; }
+    return sbc_plan_create(s.ops.data(), (int32_t)s.ops.size(), &s.plan);
+}
+
+// 7. conv_mode f16x2: per-layer activation scales (include/sbc_hip.h: sbc_f16x2_calibrate; scorenet.ScoreNet._ensure_calibrated), one
+// pass over the fixed calibration input in the first sample of the x buffer
+int calibrate(sbc_score& s) {
+    const size_t n = (size_t)s.desc.nt * s.desc.nr * s.desc.channels;
+    std::vector<float> pat(n);
+    const int rc = sbc_f16x2_calibration_input(pat.data(), (int64_t)n);
+    if (rc) return rc;
+    if (hipMemcpy(s.slots[s.tensors[s.x_t].slot], pat.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        sbc::set_error("sbc_score_create: upload of the calibration input failed");
+        return SBC_ERR_HIP;
+    }
+    return sbc_f16x2_calibrate(s.ops.data(), (int32_t)s.ops.size(), nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sbc_score_create(const sbc_score_desc* d, const sbc_tensor_ref* tensors, int32_t n_tensors, sbc_score** out) {
+    SBC_REQUIRE(d && tensors && out && n_tensors > 0, "sbc_score_create: bad arguments");
+    SBC_REQUIRE(d->ngf == 32 && d->channels == 2, "sbc_score_create: kernels are instantiated for ngf = 32, 2 channels");
+    SBC_REQUIRE(d->nt > 0 && d->nr > 0 && d->nt % 8 == 0 && d->nr % 8 == 0,
+                "sbc_score_create: Nt and Nr must be multiples of 8 (three 2x mean pools), got %dx%d", d->nt, d->nr);
+    SBC_REQUIRE(d->batch > 0 && d->conv_mode >= 0 && d->conv_mode <= 3 && d->sigmas && d->num_classes > 0,
+                "sbc_score_create: batch, conv_mode in {0 bf16x3, 1 f32, 2 f16w, 3 f16x2}, sigmas required");
+    SBC_REQUIRE(!(d->flags & SBC_SCORE_FUSE_RES) || d->conv_mode == 3, "sbc_score_create: SBC_SCORE_FUSE_RES needs conv_mode 3 (f16x2)");
+    SBC_REQUIRE(!(d->flags & SBC_SCORE_FUSE_CHAIN) || d->conv_mode == 3, "sbc_score_create: SBC_SCORE_FUSE_CHAIN needs conv_mode 3 (f16x2)");
+    SBC_REQUIRE(!(d->flags & SBC_SCORE_FUSE_DOWN) || d->conv_mode == 3, "sbc_score_create: SBC_SCORE_FUSE_DOWN needs conv_mode 3 (f16x2)");
+    SBC_REQUIRE(!(d->flags & SBC_SCORE_FUSE_PAIRS) || d->conv_mode >= 2,
+                "sbc_score_create: SBC_SCORE_FUSE_PAIRS needs the fp16 weight forms (conv_mode 2 or 3)");
+    sbc::TensorIndex sd;                     // (a name given twice: the last ref counts)
+    int rc = sd.build("sbc_score_create", tensors, n_tensors);
+    if (rc) return rc;
+    sbc_score* s = new sbc_score();
+    s->desc = *d;
+    Builder b{d->ngf, d->nt, d->nr};
+    wire(b, *s);
+    if (d->flags & SBC_SCORE_SKIP_LANES) rc = hoist_lanes(b);
+    if (!rc) {
+        s->tensors = b.t; s->pops = b.ops;
+        assign_slots(*s);
+        rc = pack_params(*s, sd);
+    }
+    if (!rc) rc = allocate(*s);
+    if (!rc) rc = bind_records(*s);
+    if (!rc && d->conv_mode == 3) rc = calibrate(*s);
+    if (rc) {
+        sbc_score_destroy(s);
+        return rc;
     }
     *out = s;
     return SBC_OK;
@@ -675,7 +677,7 @@ void sbc_score_destroy(sbc_score* s) {
     if (!s) return;
     if (s->plan) sbc_plan_destroy(s->plan);
     for (float* p : s->slots) if (p) (void)hipFree(p);
-    if (s->wdev) (void)hipFree(s->wdev);
+    s->params.release();
     if (s->sigmas) (void)hipFree(s->sigmas);
     if (s->labels) (void)hipFree(s->labels);
     delete s;

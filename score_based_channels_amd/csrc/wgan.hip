@@ -22,11 +22,10 @@
 //
 // Every stage of the last call stays readable in the caller's workspace (sbc_wgan_stage); no stage shares memory with another.
 #include "common.h"
+#include "host_params.h"
 #include <math.h>
 #include <string.h>
-#include <map>
 #include <string>
-#include <vector>
 
 namespace sbc {
 namespace {
@@ -513,28 +512,15 @@ enum { ST_ACT = 0, ST_GEN = 16, ST_DG = 17, ST_GRAD = 32, ST_MASK = 48 };
 }  // namespace sbc
 
 struct sbc_wgan {
-    int n_extra = 0, device = 0;
-    float* wdev = nullptr;
-    // offsets into wdev
+    int n_extra = 0;
+    sbc::ParamImage params;
+    // offsets into params
     size_t dense_w = 0, dense_b = 0, dense_wt = 0, out_w = 0, out_b = 0;
     size_t fwd[sbc::MAX_L + 1] = {}, adj[sbc::MAX_L + 1] = {}, bias[sbc::MAX_L + 1] = {}, bn[sbc::MAX_L + 1] = {}, scale[sbc::MAX_L + 1] = {};
 };
 
 namespace sbc {
 namespace {
-
-struct Named {
-    std::map<std::string, const sbc_tensor_ref*> sd;
-    const float* get(const std::string& name, int64_t numel, std::string* err) const {
-        auto it = sd.find(name);
-        if (it == sd.end()) { *err = "missing tensor " + name; return nullptr; }
-        if (it->second->numel != numel) {
-            *err = name + " has " + std::to_string((long long)it->second->numel) + " elements, expected " + std::to_string((long long)numel);
-            return nullptr;
-        }
-        return it->second->data;
-    }
-};
 
 // torch [co][ci][KS][KS] -> [ci / CC][tap][ci % CC][co] (forward) or, adjoint, the same packing of the flipped, transposed filter
 // w'[ci][co][ky][kx] = w[co][ci][KS - 1 - ky][KS - 1 - kx]
@@ -550,8 +536,8 @@ void pack_conv(const float* w, int KS, int CC, bool adjoint, float* out) {
 
 void conv128(const sbc_wgan* h, int k, bool bwd, const float* src, const uint32_t* mask_in, float* out, uint32_t* mask_out, int B, hipStream_t s) {
     ConvArgs a{};
-    a.src = src; a.wpk = h->wdev + (bwd ? h->adj[k] : h->fwd[k]); a.mask_in = mask_in; a.scale_in = h->wdev + h->scale[k];
-    a.bias = h->wdev + h->bias[k]; a.bn = h->wdev + h->bn[k]; a.out = out; a.mask_out = mask_out;
+    a.src = src; a.wpk = h->params.dev + (bwd ? h->adj[k] : h->fwd[k]); a.mask_in = mask_in; a.scale_in = h->params.dev + h->scale[k];
+    a.bias = h->params.dev + h->bias[k]; a.bn = h->params.dev + h->bn[k]; a.out = out; a.mask_out = mask_out;
     a.H = layer_h(k); a.W = layer_w(k); a.up = (!bwd && k <= 2) ? 1 : 0; a.bwd = bwd ? 1 : 0; a.pool = (bwd && k <= 2) ? 1 : 0;
     const dim3 grid(a.W / 32, a.H / 4, B);
     if (layer_ks(k) == 5) hipLaunchKernelGGL(conv128_kernel<5>, grid, dim3(256), 0, s, a);
@@ -571,15 +557,8 @@ struct Ws {
 
 void forward(const sbc_wgan* h, const Ws& ws, const float* z, hipStream_t s) {
     const int B = ws.B, L = ws.lay.L;
-    hipLaunchKernelGGL(dense_kernel, dim3(DENSE / 256, B), dim3(256), 0, s, z, h->wdev + h->dense_w, h->wdev + h->dense_b, ws.act(0));
+    hipLaunchKernelGGL(dense_kernel, dim3(DENSE / 256, B), dim3(256), 0, s, z, h->params.dev + h->dense_w, h->params.dev + h->dense_b, ws.act(0));
     for (int k = 1; k <= L; ++k) conv128(h, k, false, ws.act(k - 1), nullptr, ws.act(k), ws.mask(k), B, s);
-}
-
-int device_check(const sbc_wgan* h, const char* who) {
-    int dev = 0;
-    SBC_CHECK_HIP(hipGetDevice(&dev));
-    SBC_REQUIRE(dev == h->device, "%s: the handle lives on device %d, the current device is %d", who, h->device, dev);
-    return SBC_OK;
 }
 
 }  // namespace
@@ -590,26 +569,24 @@ extern "C" {
 int sbc_wgan_create(const sbc_tensor_ref* tensors, int32_t n_tensors, sbc_wgan** out) {
     using namespace sbc;
     SBC_REQUIRE(tensors && out && n_tensors > 0, "sbc_wgan_create: need tensors and out");
-    Named nm;
-    for (int i = 0; i < n_tensors; ++i) {
-        SBC_REQUIRE(tensors[i].name && tensors[i].data, "sbc_wgan_create: tensor %d has no name or data", i);
-        SBC_REQUIRE(nm.sd.emplace(tensors[i].name, &tensors[i]).second, "sbc_wgan_create: tensor %s given twice", tensors[i].name);
-    }
+    TensorIndex sd;
+    const char* twice = nullptr;
+    const int rc = sd.build("sbc_wgan_create", tensors, n_tensors, &twice);
+    if (rc) return rc;
+    SBC_REQUIRE(!twice, "sbc_wgan_create: tensor '%s' given twice", twice);
     int n_extra = 0;
-    while (nm.sd.count("conv.extra_conv" + std::to_string(n_extra) + ".weight")) ++n_extra;
+    while (sd.has("conv.extra_conv" + std::to_string(n_extra) + ".weight")) ++n_extra;
     SBC_REQUIRE(n_extra <= MAX_EXTRA, "sbc_wgan_create: at most %d extra layers are supported (got %d)", MAX_EXTRA, n_extra);
     SBC_REQUIRE(n_tensors == 16 + 5 * n_extra, "sbc_wgan_create: a generator with %d extra layers has %d float tensors (got %d)", n_extra,
                 16 + 5 * n_extra, n_tensors);
     const int L = 2 + n_extra;
     sbc_wgan* h = new sbc_wgan;
     h->n_extra = n_extra;
-    std::vector<float> host;
-    auto take = [&](size_t n) { const size_t at = host.size(); host.resize(at + ((n + 3) & ~(size_t)3), 0.f); return at; };
-    std::string err;
-    bool ok = true;
+    std::vector<float>& host = h->params.host;
+    auto take = [&](size_t n) { return h->params.take(n); };
+    bool ok = true;                                      // false after the first tensor that is missing or mis-sized: its message stays
     auto fetch = [&](const std::string& name, int64_t numel) -> const float* {
-        if (!ok) return nullptr;
-        const float* p = nm.get(name, numel, &err);
+        const float* p = ok ? sd.find(name, numel) : nullptr;
         if (!p) ok = false;
         return p;
     };
@@ -657,18 +634,10 @@ int sbc_wgan_create(const sbc_tensor_ref* tensors, int32_t n_tensors, sbc_wgan**
         h->out_b = take(2);
         memcpy(host.data() + h->out_b, b, sizeof(float) * 2);
     }
-    if (!ok) {
+    const int rc_up = ok ? h->params.upload("sbc_wgan_create") : SBC_ERR_INVALID;
+    if (rc_up) {
         delete h;
-        SBC_REQUIRE(false, "sbc_wgan_create: %s", err.c_str());
-    }
-    hipError_t e = hipGetDevice(&h->device);
-    if (e == hipSuccess) e = hipMalloc(&h->wdev, host.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(h->wdev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        set_error("sbc_wgan_create: %s", hipGetErrorString(e));
-        if (h->wdev) (void)hipFree(h->wdev);
-        delete h;
-        return SBC_ERR_HIP;
+        return rc_up;
     }
     *out = h;
     return SBC_OK;
@@ -676,7 +645,7 @@ int sbc_wgan_create(const sbc_tensor_ref* tensors, int32_t n_tensors, sbc_wgan**
 
 void sbc_wgan_destroy(sbc_wgan* h) {
     if (!h) return;
-    if (h->wdev) (void)hipFree(h->wdev);
+    h->params.release();
     delete h;
 }
 
@@ -709,14 +678,14 @@ int sbc_wgan_generate(sbc_wgan* h, const float* z, float* out, int32_t B, float*
     using namespace sbc;
     SBC_REQUIRE(h && z && out && workspace, "sbc_wgan_generate: NULL handle, z, out or workspace");
     SBC_REQUIRE(B >= 0 && B <= 32768, "sbc_wgan_generate: B must be in [0, 32768] (got %d)", B);
-    int rc = device_check(h, "sbc_wgan_generate");
+    const int rc = h->params.check_device("sbc_wgan_generate");
     if (rc) return rc;
     if (B == 0) return SBC_OK;
     hipStream_t s = (hipStream_t)stream;
     const Ws ws{workspace, B, Layout(h->n_extra)};
     forward(h, ws, z, s);
     OutArgs oa{};
-    oa.act = ws.act(ws.lay.L); oa.w = h->wdev + h->out_w; oa.bias = h->wdev + h->out_b; oa.gen = ws.gen();
+    oa.act = ws.act(ws.lay.L); oa.w = h->params.dev + h->out_w; oa.bias = h->params.dev + h->out_b; oa.gen = ws.gen();
     hipLaunchKernelGGL(out_kernel, dim3(B), dim3(256), 0, s, oa);
     SBC_CHECK_HIP(hipGetLastError());
     SBC_CHECK_HIP(hipMemcpyAsync(out, ws.gen(), sizeof(float) * 2 * PIX * (size_t)B, hipMemcpyDeviceToDevice, s));
@@ -733,7 +702,7 @@ int sbc_wgan_run(sbc_wgan* h, const sbc_wgan_run_desc* d, void* stream) {
                                                                  {d->l2_lam, "l2_lam"}, {d->loss_scale, "loss_scale"}, {d->workspace, "workspace"}};
     for (const auto& q : need) SBC_REQUIRE(q.p, "sbc_wgan_run: NULL %s", q.name);
     SBC_REQUIRE(!d->oracle_log || d->H, "sbc_wgan_run: oracle_log needs H");
-    int rc = device_check(h, "sbc_wgan_run");
+    const int rc = h->params.check_device("sbc_wgan_run");
     if (rc) return rc;
     if (d->B == 0 || d->n_steps == 0) return SBC_OK;
     hipStream_t s = (hipStream_t)stream;
@@ -744,16 +713,16 @@ int sbc_wgan_run(sbc_wgan* h, const sbc_wgan_run_desc* d, void* stream) {
         const double t = (double)d->first_step + k;
         forward(h, ws, d->z, s);
         OutArgs oa{};
-        oa.act = ws.act(L); oa.w = h->wdev + h->out_w; oa.bias = h->wdev + h->out_b; oa.P = d->P; oa.Y = d->Y; oa.Htrue = d->H;
+        oa.act = ws.act(L); oa.w = h->params.dev + h->out_w; oa.bias = h->params.dev + h->out_b; oa.P = d->P; oa.Y = d->Y; oa.Htrue = d->H;
         oa.loss_scale = d->loss_scale; oa.gen = ws.gen(); oa.dG = ws.dg();
         oa.meas_log = d->meas_log ? d->meas_log + (size_t)k * B : nullptr;
         oa.oracle_log = d->oracle_log ? d->oracle_log + (size_t)k * B : nullptr;
         oa.Np = d->Np; oa.run = 1;
         hipLaunchKernelGGL(out_kernel, dim3(B), dim3(256), 0, s, oa);
-        hipLaunchKernelGGL(out_adjoint_kernel, dim3(CH / OA_CG, B), dim3(256), 0, s, ws.dg(), h->wdev + h->out_w, ws.grad(L));
+        hipLaunchKernelGGL(out_adjoint_kernel, dim3(CH / OA_CG, B), dim3(256), 0, s, ws.dg(), h->params.dev + h->out_w, ws.grad(L));
         for (int l = L; l >= 1; --l) conv128(h, l, true, ws.grad(l), ws.mask(l), ws.grad(l - 1), nullptr, B, s);
         AdamArgs aa{};
-        aa.g0 = ws.grad(0); aa.Wt = h->wdev + h->dense_wt; aa.z = d->z; aa.m = d->m; aa.v = d->v;
+        aa.g0 = ws.grad(0); aa.Wt = h->params.dev + h->dense_wt; aa.z = d->z; aa.m = d->m; aa.v = d->v;
         aa.lr = d->lr; aa.lam = d->l2_lam; aa.scale = d->loss_scale;
         aa.reg_log = d->reg_log ? d->reg_log + (size_t)k * B : nullptr;
         aa.z_log = d->z_log ? d->z_log + (size_t)k * B * NZ : nullptr;

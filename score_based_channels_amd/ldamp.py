@@ -81,15 +81,7 @@ def check_hparams(hparams):
 
 def check_state_dict(sd, max_unrolls):
     """Raise ``KeyError`` / ``ValueError`` like ``load_state_dict(strict=True)`` would."""
-    spec = state_dict_spec(max_unrolls)
-    names = dict(spec)
-    missing = [n for n, _ in spec if n not in sd]
-    unexpected = [n for n in sd if n not in names]
-    if missing or unexpected:
-        raise KeyError('state_dict mismatch: missing %s, unexpected %s' % (missing[:5], unexpected[:5]))
-    for n, shape in spec:
-        if tuple(sd[n].shape) != tuple(shape):
-            raise ValueError('size mismatch for %s: %s vs %s' % (n, tuple(sd[n].shape), tuple(shape)))
+    _lib.check_against_spec(sd, state_dict_spec(max_unrolls))
 
 
 def check_run_args(Y_shape, P_shape, eig_shape, num_unrolls, max_unrolls, directions_shape=None):
@@ -130,64 +122,27 @@ def stage_layout(stage, n_images):
     return off.value, (int(n_images), c.value, h.value, w.value)
 
 
-class LDAMP:
+class LDAMP(_lib.DeviceHandle):
     """``LDAMP(hparams)`` / ``load_state_dict`` / ``eval`` / ``__call__(sample, num_unrolls)`` as the reference module; additions:
     ``directions=`` (float32 ``[num_unrolls, B, 64, 16, 2]``: the random directions instead of device draws), ``seed=`` and
     ``sample_ids=`` (key of the device draws: direction of sample ``b`` at unroll ``u`` = Philox stream ``(seed, sample_ids[b], u)``,
     default ids ``0 .. B-1``), ``return_logs=`` (also return a dict of per-unroll ``h``, ``z``, ``div``, ``eps``) and ``H=`` (the true
     channels: the per-sample NMSE is added to the logs as ``nmse``)."""
 
+    _destroy = 'sbc_ldamp_destroy'
+
     def __init__(self, hparams, device=None):
+        super().__init__(device)
         self.max_unrolls = check_hparams(hparams)
-        self.device = device
-        self._h = None
-        self._ws = None
-        self.last_workspace = None                       # (tensor, n_images) of the last call, for stage()
-
-    def cuda(self, device=None):
-        self.device = device if device is not None else self.device
-        return self
-
-    def eval(self):
-        return self
 
     def load_state_dict(self, model_state):
-        import torch
-        sd = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in model_state.items()}
+        sd = _lib.numpy_state_dict(model_state)
         check_state_dict(sd, self.max_unrolls)
-        spec = state_dict_spec(self.max_unrolls)
-        keep = [np.ascontiguousarray(sd[n], dtype=np.float32) for n, _ in spec]
-        names = [n.encode() for n, _ in spec]
-        refs = (_lib.sbc_tensor_ref * len(spec))(*[_lib.sbc_tensor_ref(names[i], keep[i].ctypes.data_as(C.c_void_p), keep[i].size)
-                                                   for i in range(len(spec))])
-        dev = self._torch_device()
-        handle = C.c_void_p()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().sbc_ldamp_create(refs, len(spec), self.max_unrolls, C.byref(handle)))
-        self.close()
-        self._h = handle
-        return self
-
-    def _torch_device(self):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError('LDAMP needs a HIP device (there is no CPU fallback)')
-        d = self.device
-        if d is None:
-            return torch.device('cuda', torch.cuda.current_device())
-        d = torch.device(d)
-        return d if d.index is not None else torch.device('cuda', torch.cuda.current_device())
-
-    def _need_weights(self):
-        if self._h is None:
-            raise RuntimeError('LDAMP has no weights: call load_state_dict first')
+        return self._load(sd, [n for n, _ in state_dict_spec(self.max_unrolls)],
+                          lambda refs, n, out: _lib.lib().sbc_ldamp_create(refs, n, self.max_unrolls, out))
 
     def _workspace(self, B, unrolls, dev):
-        import torch
-        n = int(_lib.lib().sbc_ldamp_workspace_floats(int(B), int(unrolls)))
-        if self._ws is None or self._ws.numel() < n or self._ws.device != dev:
-            self._ws = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-        return self._ws
+        return self._workspace_of(_lib.lib().sbc_ldamp_workspace_floats(int(B), int(unrolls)), dev)
 
     def denoise(self, net, r, stream=None):
         """``D_net(r)`` for complex64 ``r`` ``[B, 64, 16]`` -> complex64 ``[B, 64, 16]`` (one evaluation; asynchronous)."""
@@ -278,14 +233,3 @@ class LDAMP:
                     t.record_stream(s)
         self.last_workspace = (ws, 2 * B)
         return (H_hat, logs) if (return_logs or H is not None) else H_hat
-
-    def close(self):
-        if self._h:
-            _lib.lib().sbc_ldamp_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

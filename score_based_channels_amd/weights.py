@@ -11,6 +11,8 @@ fixed numpy bit-generator ("seed-derived weights").
 """
 import numpy as np
 
+from ._lib import check_against_spec
+
 
 def _residual_block(prefix, cin, cout, resample, dilation):
     """Tensor list of one ResidualBlock, in ``state_dict`` order (layers.py:401-441)."""
@@ -113,14 +115,7 @@ def seeded_state_dict(config, seed=2024):
 
 def check_state_dict(sd, config):
     """Raise ``KeyError``/``ValueError`` like ``load_state_dict(strict=True)`` would."""
-    spec = state_dict_spec(config.model.ngf, config.data.channels, config.model.num_classes)
-    missing = [n for n, _ in spec if n not in sd]
-    unexpected = [n for n in sd if n not in dict(spec)]
-    if missing or unexpected:
-        raise KeyError('state_dict mismatch: missing %s, unexpected %s' % (missing[:5], unexpected[:5]))
-    for n, shape in spec:
-        if tuple(sd[n].shape) != tuple(shape):
-            raise ValueError('size mismatch for %s: %s vs %s' % (n, tuple(sd[n].shape), shape))
+    check_against_spec(sd, state_dict_spec(config.model.ngf, config.data.channels, config.model.num_classes))
 
 
 def pack_conv_weight(w):

@@ -92,15 +92,7 @@ def check_geometry(isize, nz, nc, ngf, n_extra_layers=0):
 
 def check_state_dict(sd, n_extra):
     """Raise ``KeyError`` / ``ValueError`` like ``load_state_dict(strict=True)`` would."""
-    spec = state_dict_spec(n_extra)
-    names = dict(spec)
-    missing = [n for n, _ in spec if n not in sd]
-    unexpected = [n for n in sd if n not in names]
-    if missing or unexpected:
-        raise KeyError('state_dict mismatch: missing %s, unexpected %s' % (missing[:5], unexpected[:5]))
-    for n, shape in spec:
-        if tuple(np.shape(sd[n])) != tuple(shape):
-            raise ValueError('size mismatch for %s: %s vs %s' % (n, tuple(np.shape(sd[n])), tuple(shape)))
+    _lib.check_against_spec(sd, state_dict_spec(n_extra))
 
 
 def check_run_args(z_shape, Y_shape, P_shape, steps, H_shape=None, first_step=1):
@@ -162,65 +154,27 @@ def unpack_mask(words, width):
     return bits.reshape(w.shape[:-1] + (width,)).astype(bool)
 
 
-class DCGAN_G_Ours:
+class DCGAN_G_Ours(_lib.DeviceHandle):
     """``DCGAN_G_Ours(isize, nz, nc, ngf, ngpu, n_extra_layers)`` / ``load_state_dict`` / ``cuda`` / ``eval`` / ``__call__(z)`` as the
     reference module.  ``z``: float32 ``[B, 60, 1, 1]`` or ``[B, 60]`` (B = 1 also after the reference's ``squeeze``: ``[60]``) ->
     ``[B, 2, 16, 64]``.  ``stage(name)`` returns a view of the last call's workspace."""
 
+    _destroy = 'sbc_wgan_destroy'
+
     def __init__(self, isize, nz, nc, ngf, ngpu=1, n_extra_layers=0, device=None):
+        super().__init__(device)
         self.n_extra = check_geometry(isize, nz, nc, ngf, n_extra_layers)
         self.Nr, self.Nt = NR, NT
         self.ngpu = ngpu
-        self.device = device
-        self._h = None
-        self._ws = None
-        self.last_workspace = None                       # (tensor, B) of the last call, for stage()
-
-    def cuda(self, device=None):
-        self.device = device if device is not None else self.device
-        return self
-
-    def eval(self):
-        return self
 
     def load_state_dict(self, state):
-        import torch
-        sd = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in state.items()}
+        sd = _lib.numpy_state_dict(state)
         check_state_dict(sd, self.n_extra)
-        spec = [(n, s) for n, s in state_dict_spec(self.n_extra) if not n.endswith('num_batches_tracked')]
-        keep = [np.ascontiguousarray(sd[n], dtype=np.float32) for n, _ in spec]
-        names = [n.encode() for n, _ in spec]
-        refs = (_lib.sbc_tensor_ref * len(spec))(*[_lib.sbc_tensor_ref(names[i], keep[i].ctypes.data_as(C.c_void_p), keep[i].size)
-                                                   for i in range(len(spec))])
-        dev = self._torch_device()
-        handle = C.c_void_p()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().sbc_wgan_create(refs, len(spec), C.byref(handle)))
-        self.close()
-        self._h = handle
-        return self
-
-    def _torch_device(self):
-        import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError('DCGAN_G_Ours needs a HIP device (there is no CPU fallback)')
-        d = self.device
-        if d is None:
-            return torch.device('cuda', torch.cuda.current_device())
-        d = torch.device(d)
-        return d if d.index is not None else torch.device('cuda', torch.cuda.current_device())
-
-    def _need_weights(self):
-        if self._h is None:
-            raise RuntimeError('DCGAN_G_Ours has no weights: call load_state_dict first')
+        return self._load(sd, [n for n, _ in state_dict_spec(self.n_extra) if not n.endswith('num_batches_tracked')],
+                          _lib.lib().sbc_wgan_create)
 
     def _workspace(self, B, dev):
-        import torch
-        n = int(_lib.lib().sbc_wgan_workspace_floats(self._h, int(B)))
-        if self._ws is None or self._ws.numel() < n or self._ws.device != dev:
-            self._ws = None
-            self._ws = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-        return self._ws
+        return self._workspace_of(_lib.lib().sbc_wgan_workspace_floats(self._h, int(B)), dev)
 
     def _latents(self, z, dev):
         import torch
@@ -268,17 +222,6 @@ class DCGAN_G_Ours:
         if name.startswith('mask'):
             t = t.view(torch.int32)
         return t.view(B, c.value, h.value, w.value)
-
-    def close(self):
-        if self._h:
-            _lib.lib().sbc_wgan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class LatentOptimizer:

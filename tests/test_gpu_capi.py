@@ -15,14 +15,12 @@ MODES = {'bf16x3': 0, 'f32': 1, 'f16w': 2, 'f16x2': 3}
 
 def _create(sd, cfg, B, nt, nr, mode, pairs=False, fold=False, res=False, chain=False, down=False, end=False, lanes=False):
     from score_based_channels_amd import _lib
-    keep = {k: np.ascontiguousarray(v, np.float32) for k, v in sd.items() if k != 'sigmas'}
-    refs = (_lib.sbc_tensor_ref * len(keep))(*[
-        _lib.sbc_tensor_ref(name=k.encode(), data=v.ctypes.data, numel=v.size) for k, v in keep.items()])
+    refs, keep = _lib.tensor_refs(sd, [k for k in sd if k != 'sigmas'])
     sig = np.ascontiguousarray(sd['sigmas'], np.float32)
     desc = _lib.sbc_score_desc(ngf=32, channels=2, nt=nt, nr=nr, batch=B, conv_mode=MODES[mode], sigmas=sig.ctypes.data,
                                num_classes=sig.size, flags=(1 if pairs else 0) | (2 if fold else 0) | (4 if res else 0) | (8 if chain else 0) | (16 if down else 0) | (32 if end else 0) | (64 if lanes else 0))
     h = C.c_void_p()
-    _lib.check(_lib.lib().sbc_score_create(C.byref(desc), refs, len(keep), C.byref(h)))
+    _lib.check(_lib.lib().sbc_score_create(C.byref(desc), refs, len(refs), C.byref(h)))
     return h
 
 
