@@ -304,9 +304,14 @@ static int launch_wino_sized(const ConvParams& p, hipStream_t stream, bool dry) 
     constexpr bool mb2_ok = (COUT == 32);          // 256-pixel tiles only where one output block keeps registers low
     // 256-pixel tiles for the full-resolution level only (>= 4096 tiles); 128-pixel tiles measure within 2 % below that
     // and keep one kernel symbol per level, so per-kernel profiler averages are per level too
-    if (mb2_ok && fits(256) && p.total_px >= 256L * 4096) return launch_wino<CIN, COUT, 2>(p, stream, dry);
+    // (`if constexpr`: the 256-pixel form is not compiled for the channel counts that can never select it)
+    if constexpr (mb2_ok) {
+        if (fits(256) && p.total_px >= 256L * 4096) return launch_wino<CIN, COUT, 2>(p, stream, dry);
+    }
     if (fits(128)) return launch_wino<CIN, COUT, 1>(p, stream, dry);
-    if (mb2_ok && fits(256)) return launch_wino<CIN, COUT, 2>(p, stream, dry);
+    if constexpr (mb2_ok) {
+        if (fits(256)) return launch_wino<CIN, COUT, 2>(p, stream, dry);
+    }
     return 1;
 }
 

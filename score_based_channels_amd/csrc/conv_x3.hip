@@ -263,25 +263,42 @@ static size_t x3_lds_bytes(const ConvParams& p, int* plane_out) {
     return staged > epi ? staged : epi;
 }
 
+// Can any record select this form within the 160 KiB of LDS?  Its smallest tile has no halo.  A tile above launch_sized's 80 KiB rule is
+// reached only through its fall-back chain, i.e. with rows of at least TM / 2 pixels (W = TM, or W = TM / 2 pooled); an image that is not
+// a power of two is then larger than the tile (an image that divides the tile is a power of two), so generic index math (P2 = false)
+// brings a 3x3 halo of at least TM pixels.  Forms that fail this are not compiled: their records are refused as before.
+template <int CIN, int COUT, int KS, int TM, bool P2, int TERMS>
+constexpr bool x3_selectable() {
+    constexpr long SH2 = (CIN + 8) * 2, staged = TERMS * (TM + 1) * SH2, epi = (long)TM * (COUT + 4) * 4;
+    constexpr long lds_min = staged > epi ? staged : epi;
+    if (lds_min > 160 * 1024) return false;
+    if (P2 || KS == 1 || TM == 64 || lds_min <= 80 * 1024) return true;
+    return TERMS * (2 * TM + 1) * SH2 <= 160 * 1024;
+}
+
 template <int CIN, int COUT, int KS, int MT, int NT, int WM, int WN, bool P2, int TERMS>
 static int launch_kernel(ConvParams p, hipStream_t stream, bool dry) {
     constexpr int TM = 32 * MT * WM;
     size_t lds = x3_lds_bytes<CIN, COUT, KS, MT, NT, WM, WN, TERMS>(p, &p.plane);
-    if (p.flags & SBC_PRO_NORM_SELF) {
-        const int HW = p.H * p.W;
-        SBC_REQUIRE(TM % HW == 0, "conv: SBC_PRO_NORM_SELF needs tiles of whole samples (H*W = %d, tile %d)", HW, TM);
-        lds = (lds + 15) / 16 * 16;
-        p.stats_off = (int)(lds / sizeof(float));
-        lds += (size_t)(TM / HW) * (3 * CIN + 2) * sizeof(float);
+    if constexpr (!x3_selectable<CIN, COUT, KS, TM, P2, TERMS>()) {
+        SBC_REQUIRE(false, "conv tile needs %zu bytes of LDS (> 160 KiB)", lds);
+    } else {
+        if (p.flags & SBC_PRO_NORM_SELF) {
+            const int HW = p.H * p.W;
+            SBC_REQUIRE(TM % HW == 0, "conv: SBC_PRO_NORM_SELF needs tiles of whole samples (H*W = %d, tile %d)", HW, TM);
+            lds = (lds + 15) / 16 * 16;
+            p.stats_off = (int)(lds / sizeof(float));
+            lds += (size_t)(TM / HW) * (3 * CIN + 2) * sizeof(float);
+        }
+        SBC_REQUIRE(lds <= 160 * 1024, "conv tile needs %zu bytes of LDS (> 160 KiB)", lds);
+        auto kern = conv_x3_kernel<CIN, COUT, KS, MT, NT, WM, WN, P2, TERMS>;
+        { const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
+        if (dry) return SBC_OK;
+        const int grid = (p.total_px + TM - 1) / TM;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WM * WN), lds, stream, p);
+        SBC_CHECK_HIP(hipGetLastError());
+        return SBC_OK;
     }
-    SBC_REQUIRE(lds <= 160 * 1024, "conv tile needs %zu bytes of LDS (> 160 KiB)", lds);
-    auto kern = conv_x3_kernel<CIN, COUT, KS, MT, NT, WM, WN, P2, TERMS>;
-    { const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
-    if (dry) return SBC_OK;
-    const int grid = (p.total_px + TM - 1) / TM;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WM * WN), lds, stream, p);
-    SBC_CHECK_HIP(hipGetLastError());
-    return SBC_OK;
 }
 
 template <int CIN, int COUT, int KS, int MT, int NT, int WM, int WN>
@@ -301,6 +318,9 @@ static int launch_variant(const ConvParams& p, hipStream_t stream, bool dry) {
 
 // Tile choice: the largest tile that fits the image, keeps >= 2 workgroups per CU worth of work (256 CUs) and leaves
 // room for two workgroups in the 160 KiB of LDS.
+// x3_selectable (above) restates which (tile, index math, terms) this choice can reach inside the LDS and keeps the rest from being
+// compiled: change the tile sizes, `fits`, the 80 KiB rule or the fall-back chain here and x3_selectable has to follow, or a record this
+// function selects is refused (tests/test_gpu_ops.py launches every compiled form, test_host_logic.py the refused ones).
 template <int CIN, int COUT, int KS>
 static int launch_sized(const ConvParams& p, hipStream_t stream, bool dry) {
     constexpr int NB = COUT / 32;

@@ -101,9 +101,86 @@ CONV_CASES = [
 ]
 
 
-@pytest.mark.parametrize('algo', ['direct', 'winograd', 'bf16x3', 'winograd_bf16x3', 'f16w', 'winograd_f16w', 'f16x2',
-                                  'winograd_f16x2'])
-@pytest.mark.parametrize('cin,cout,k,dil,B,H,W,mode', CONV_CASES)
+CONV_ALGOS = ['direct', 'winograd', 'bf16x3', 'winograd_bf16x3', 'f16w', 'winograd_f16w', 'f16x2', 'winograd_f16x2']
+
+# Records for the kernel instantiations that CONV_CASES x CONV_ALGOS does not select (profiles/kernel_coverage.txt; the dispatch is
+# launch_sized / launch_variant of conv_x3.hip and conv_mfma.hip, launch_wino_sized, launch_wx3_sized / launch_wx3), each with the algos
+# that reach something new.  Smallest records: a 128- or 256-pixel tile is selected for a small batch where no smaller tile holds whole
+# rows (W = 128; W = 64 or 128 pooled) and for any shape from 65 536 / 131 072 pixels on; H = 3, 6, 24, 48 is generic index math.
+# A mode ending in '_top' sets sbc_op.tag = 1 (the full-resolution level's own kernel symbols); 'winograd_raw_f16w' is the record of
+# the f16w Winograd form alone: fp32 weight + fp16 Winograd filter, no direct fp16 weight (with one, the direct kernel takes the layer).
+CONV_EXTRA = [
+    ((32, 32, 3, 1, 2, 2, 8, 'norm_elu_res'), 'winograd_raw_f16w'),
+    ((32, 32, 3, 1, 2, 2, 8, 'norm_elu_res_top'), 'winograd_bf16x3 winograd_f16x2 winograd_raw_f16w'),
+    ((32, 32, 3, 1, 2, 2, 128, 'norm_elu_res'), 'direct winograd bf16x3 winograd_bf16x3 f16w f16x2 winograd_f16x2 winograd_raw_f16w'),
+    ((32, 32, 3, 1, 2, 2, 128, 'norm_elu_res_top'), 'winograd_bf16x3 winograd_f16x2 winograd_raw_f16w'),
+    ((32, 32, 3, 1, 2, 3, 128, 'norm_elu_res'), 'direct bf16x3 f16w f16x2'),
+    ((32, 32, 3, 1, 2, 6, 128, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((32, 64, 1, 1, 2, 2, 64, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((32, 64, 1, 1, 2, 2, 128, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((32, 64, 1, 1, 2, 3, 128, 'norm_elu_res'), 'direct bf16x3 f16w f16x2'),
+    ((32, 64, 1, 1, 2, 6, 128, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((32, 64, 1, 1, 2, 24, 8, 'norm_elu_res'), 'direct bf16x3 f16w f16x2'),
+    ((32, 64, 3, 1, 2, 2, 64, 'pool'), 'direct bf16x3 f16w f16x2 winograd_raw_f16w'),
+    ((32, 64, 3, 1, 2, 3, 128, 'norm_elu_res'), 'direct bf16x3 f16w f16x2'),
+    ((32, 64, 3, 1, 2, 6, 128, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((32, 64, 3, 1, 4097, 2, 8, 'norm_elu_res'), 'winograd_raw_f16w'),
+    ((64, 32, 1, 1, 2, 2, 8, 'norm_elu_res'), 'bf16x3 f16w f16x2'),
+    ((64, 32, 1, 1, 2, 2, 64, 'pool'), 'bf16x3 f16w f16x2'),
+    ((64, 32, 1, 1, 2, 2, 128, 'pool'), 'bf16x3 f16w f16x2'),
+    ((64, 32, 1, 1, 2, 3, 128, 'norm_elu_res'), 'bf16x3 f16w f16x2'),
+    ((64, 32, 1, 1, 2, 6, 128, 'pool'), 'bf16x3 f16w f16x2'),
+    ((64, 32, 1, 1, 2, 24, 8, 'norm_elu_res'), 'bf16x3 f16w f16x2'),
+    ((64, 32, 3, 1, 2, 2, 64, 'pool'), 'direct bf16x3 f16w f16x2 winograd_raw_f16w'),
+    ((64, 32, 3, 1, 2, 2, 128, 'pool'), 'direct winograd bf16x3 winograd_bf16x3 f16w f16x2 winograd_f16x2 winograd_raw_f16w'),
+    ((64, 32, 3, 1, 2, 6, 64, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((64, 32, 3, 1, 2, 6, 128, 'pool'), 'direct f16w f16x2'),
+    ((64, 32, 3, 1, 2, 24, 8, 'norm_elu_res'), 'direct bf16x3 f16w f16x2'),
+    ((64, 64, 1, 1, 2, 2, 64, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((64, 64, 1, 1, 2, 2, 128, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((64, 64, 1, 1, 2, 3, 128, 'norm_elu_res'), 'direct bf16x3 f16w f16x2'),
+    ((64, 64, 1, 1, 2, 6, 128, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((64, 64, 1, 1, 2, 24, 8, 'norm_elu_res'), 'direct bf16x3 f16w f16x2'),
+    ((64, 64, 3, 1, 2, 2, 8, 'norm_elu_res'), 'winograd_raw_f16w'),
+    ((64, 64, 3, 1, 2, 2, 128, 'pool'), 'bf16x3 f16x2'),
+    ((64, 64, 3, 1, 2, 6, 64, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((64, 64, 3, 1, 2, 6, 128, 'pool'), 'direct f16w f16x2'),
+    ((64, 64, 3, 1, 4097, 2, 8, 'norm_elu_res'), 'winograd_raw_f16w'),
+    ((64, 128, 3, 1, 2, 2, 64, 'pool'), 'direct winograd bf16x3 winograd_bf16x3 f16w f16x2 winograd_f16x2 winograd_raw_f16w'),
+    ((64, 128, 3, 1, 2, 2, 128, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((64, 128, 3, 1, 2, 6, 64, 'pool'), 'direct bf16x3 f16w f16x2'),
+    ((64, 128, 3, 1, 2, 6, 128, 'pool'), 'direct f16w f16x2'),
+    ((64, 128, 3, 1, 2, 24, 8, 'norm_elu_res'), 'direct bf16x3 f16w f16x2'),
+    ((64, 128, 3, 1, 4097, 2, 8, 'norm_elu_res'), 'winograd_bf16x3 winograd_f16x2 winograd_raw_f16w'),
+    ((128, 64, 3, 1, 2, 2, 64, 'pool'), 'direct bf16x3 f16w f16x2 winograd_raw_f16w'),
+    ((128, 64, 3, 1, 2, 2, 128, 'pool'), 'direct f16w f16x2'),
+    ((128, 64, 3, 1, 2, 6, 64, 'pool'), 'direct f16w f16x2'),
+    ((128, 64, 3, 1, 2, 6, 128, 'pool'), 'f16w'),
+    ((128, 64, 3, 1, 2, 24, 8, 'norm_elu_res'), 'direct bf16x3 f16w f16x2'),
+    ((128, 64, 3, 1, 172, 48, 16, 'norm_elu_res'), 'direct'),
+    ((128, 64, 3, 1, 4097, 2, 8, 'norm_elu_res'), 'winograd_bf16x3 winograd_f16x2 winograd_raw_f16w'),
+    ((128, 128, 3, 1, 2, 2, 64, 'pool'), 'direct bf16x3 winograd_raw_f16w'),
+    ((128, 128, 3, 1, 2, 2, 128, 'pool'), 'direct f16w f16x2'),
+    ((128, 128, 3, 1, 2, 6, 64, 'pool'), 'direct f16w f16x2'),
+    ((128, 128, 3, 1, 2, 6, 128, 'pool'), 'f16w'),
+    ((128, 128, 3, 1, 2, 24, 8, 'norm_elu_res'), 'direct bf16x3 f16w f16x2'),
+    ((128, 128, 3, 1, 172, 48, 16, 'norm_elu_res'), 'direct'),
+    ((128, 128, 3, 1, 4097, 2, 8, 'norm_elu_res'), 'winograd_bf16x3 winograd_f16x2 winograd_raw_f16w'),
+    # The 256-pixel Winograd forms where a 128-wide level runs them: an image larger than the tile (8 x 128, four tiles per sample), so
+    # the tile is staged with its halo rows (clipped at the sample's first and last row), the T planes sit behind TM + 2 W + 1 staged
+    # pixels, and the norm prologue reads one sample's statistics per tile -- the 2 x 128 records above are one whole sample per tile
+    # and take none of that.  Then 520 tiles (more than two per CU), and the fp32 form at its 2^20-pixel threshold (4096 tiles).
+    ((32, 32, 3, 1, 3, 8, 128, 'norm_elu_res'), 'winograd winograd_bf16x3 winograd_f16x2 winograd_raw_f16w'),
+    ((32, 32, 3, 1, 3, 8, 128, 'norm_elu_res_top'), 'winograd_bf16x3 winograd_f16x2 winograd_raw_f16w'),
+    ((64, 32, 3, 1, 3, 8, 128, 'up_same'), 'winograd winograd_bf16x3 winograd_f16x2 winograd_raw_f16w'),
+    ((32, 32, 3, 1, 130, 8, 128, 'elu_res'), 'winograd winograd_bf16x3 winograd_f16x2'),
+    ((32, 32, 3, 1, 1024, 64, 16, 'elu_res'), 'winograd'),
+]
+
+CONV_PARAMS = [c + (a,) for c in CONV_CASES for a in CONV_ALGOS] + [c + (a,) for c, algos in CONV_EXTRA for a in algos.split()]
+
+
+@pytest.mark.parametrize('cin,cout,k,dil,B,H,W,mode,algo', CONV_PARAMS)
 def test_conv_matches_oracle(gpu, cin, cout, k, dil, B, H, W, mode, algo):
     """The three multipliers behind SBC_OP_CONV: the fp32-MFMA direct implicit GEMM (weight); when the op also carries
     weight_wino, fp32 Winograd F(2x2,3x3) for undilated 3x3 convs (shapes it does not cover fall back to direct); and,
@@ -149,7 +226,9 @@ def test_conv_matches_oracle(gpu, cin, cout, k, dil, B, H, W, mode, algo):
         tol = 1e-4 if algo == 'f16w' else 4e-3
     else:
         w_ref, v_ref = w, v
-    ref = O.conv2d(v_ref.transpose(0, 3, 1, 2), w_ref, bias, dil)
+    # (in chunks of samples: the oracle builds an im2col of everything it is given)
+    step = max(1, (1 << 17) // (H * W))
+    ref = np.concatenate([O.conv2d(v_ref[i:i + step].transpose(0, 3, 1, 2), w_ref, bias, dil) for i in range(0, B, step)])
     if pool:
         flags |= P.EPI_POOL
         ref = O.mean_pool2(ref)
@@ -179,6 +258,14 @@ def test_conv_matches_oracle(gpu, cin, cout, k, dil, B, H, W, mode, algo):
             setattr(op, name, _p(d[name]))
     if up is not None:
         op.up_h, op.up_w = up.shape[1], up.shape[2]
+    if mode.endswith('_top'):
+        op.tag = 1
+    if algo == 'winograd_raw_f16w':
+        # (the record keeps its fp32 `weight`, which the ABI requires: were conv_wx3 to decline the shape, the fp32 direct kernel would
+        # take it and pass these bounds.  That the f16w Winograd forms run for these records is what profiles/kernel_coverage.txt and
+        # tests/test_kernel_coverage_cpu.py hold: no other test launches them)
+        wwf = _dev(torch, pack_conv_weight_winograd_f16(w).view(np.float32))
+        op.weight_wino_split, op.flags = _p(wwf), flags | P.CONV_F16W
     if algo == 'winograd':
         ww = _dev(torch, pack_conv_weight_winograd(w))
         op.weight_wino = _p(ww)
@@ -213,7 +300,7 @@ def test_conv_matches_oracle(gpu, cin, cout, k, dil, B, H, W, mode, algo):
     # and element by element for every output of at least 5 % of the largest magnitude: a 5x tighter statement than the
     # norm-wise bound implies for those elements
     # (fp16 kernels: a staged value one fp32 ulp off may round to the neighbouring fp16, a 2^-11 change of one product)
-    assert rel_err_elementwise(got, ref, 0.05) < {'f16w': 4e-3, 'winograd_f16w': 4e-2}.get(algo, 4 * tol)
+    assert rel_err_elementwise(got, ref, 0.05) < {'f16w': 4e-3, 'winograd_f16w': 4e-2, 'winograd_raw_f16w': 4e-2}.get(algo, 4 * tol)
 
 
 @pytest.mark.parametrize('cin,cout,B', [(128, 128, 53), (64, 128, 53), (128, 64, 53), (64, 64, 120)])
@@ -267,6 +354,11 @@ def test_conv_rejects_unsupported_shapes(gpu):
     assert rc == -3 and b'no kernel' in _lib.lib().sbc_last_error()
     op = _lib.sbc_op(kind=P.CONV, B=1, H=8, W=8, cin=32, cout=32, ksize=5, dil=1, in_=_p(t), out=_p(t), weight=_p(t))
     assert _lib.lib().sbc_op_launch(C.byref(op), None) == -1
+    # forms that conv_x3.hip does not compile because no tile of theirs fits the LDS (x3_selectable; the three-term ones: test_host_logic.py)
+    for cout in (128, 64):
+        op = _lib.sbc_op(kind=P.CONV, flags=P.EPI_POOL | P.CONV_F16X2, B=2, H=6, W=128, cin=128, cout=cout, ksize=3, dil=1, in_=_p(t), out=_p(t),
+                         weight_split=_p(t))
+        assert _lib.lib().sbc_op_launch(C.byref(op), None) == -1 and b'bytes of LDS (> 160 KiB)' in _lib.lib().sbc_last_error()
 
 
 @pytest.mark.parametrize('C_,B,H,W', [(32, 5, 64, 16), (64, 3, 32, 8), (64, 4, 16, 4), (128, 7, 8, 2), (32, 1, 256, 64)])

@@ -352,6 +352,27 @@ def test_library_contains_no_packed_fp32_instructions():
     assert 'no packed-fp32 arithmetic' in p.stdout
 
 
+def test_conv_forms_beyond_the_lds_are_refused_not_compiled():
+    """csrc/conv_x3.hip does not compile the split-bf16 direct forms whose smallest tile exceeds the 160 KiB of LDS (x3_selectable): the
+    records that select them are refused with the LDS message, as they were when the forms existed.  Nine of the eleven forms (the two
+    two-term ones need the device's range flag first: tests/test_gpu_ops.py): a 256-pixel tile with 128 input channels (2 x 128 pooled), and
+    generic index math with a 256-pixel tile (6 x 128 pooled) or a 128-pixel tile with 128 input channels (6 x 64 pooled).  No GPU needed:
+    the dispatch refuses before any HIP call."""
+    import ctypes as C
+    from score_based_channels_amd import _lib, plan as P
+    # (a small HOST buffer stands for every tensor: this relies on launch_sized / launch_kernel refusing before anything is launched, here
+    # and on a machine with a GPU.  A dispatch change that came to accept one of these records would launch on host pointers: change this
+    # list with it)
+    buf = np.zeros(64, np.float32)
+    p = C.c_void_p(buf.ctypes.data)
+    for cin, cout, H, W in [(128, 128, 2, 128), (128, 64, 2, 128), (128, 128, 6, 128), (128, 64, 6, 128), (64, 128, 6, 128), (64, 32, 6, 128),
+                            (64, 64, 6, 128), (128, 128, 6, 64), (128, 64, 6, 64)]:
+        op = _lib.sbc_op(kind=P.CONV, flags=P.EPI_POOL, B=2, H=H, W=W, cin=cin, cout=cout, ksize=3, dil=1, in_=p, out=p, weight_split=p)
+        rc = _lib.lib().sbc_op_launch(C.byref(op), None)
+        msg = _lib.lib().sbc_last_error().decode()
+        assert rc == -1 and 'bytes of LDS (> 160 KiB)' in msg, (cin, cout, H, W, rc, msg)
+
+
 def test_training_plan_covers_every_parameter_exactly_once():
     """train.TrainNet without a GPU: the flat parameter layout round-trips a state_dict, and the reverse
     records write the gradient of every parameter tensor exactly once (conv weights / biases through CONV_WGRAD or the
