@@ -25,7 +25,8 @@
  *
  * Beside the plan interface the library carries the other estimators of the paper's Fig. 5c, each a self-contained group of calls
  * with its own section below: the lifted-DFT l1 solver and regularised least squares (sbc_l1_lifted_run, sbc_ls_regularized), Learned
- * D-AMP (sbc_ldamp_*) and the WGAN latent optimisation (sbc_wgan_*: generator forward, backward and Adam on the latents).  The two
+ * D-AMP (sbc_ldamp_*) and the WGAN latent optimisation (sbc_wgan_*: generator forward, backward and Adam on the latents; sbc_wgan_trainer_*:
+ * the critic and generator iterations that train that generator).  The
  * network baselines keep their activations planar, [N][C][H][W] float32, in a workspace the caller owns.
  */
 #ifndef SBC_HIP_H
@@ -703,6 +704,71 @@ int64_t sbc_wgan_workspace_floats(const sbc_wgan* handle, int32_t B);
 int sbc_wgan_generate(sbc_wgan* handle, const float* z, float* out, int32_t B, float* workspace, void* stream);
 int sbc_wgan_run(sbc_wgan* handle, const sbc_wgan_run_desc* desc, void* stream);
 int sbc_wgan_stage(const sbc_wgan* handle, int32_t stage, int32_t B, int64_t* offset, int32_t* channels, int32_t* height, int32_t* width);
+
+/* --- WGAN training ----------------------------------------------------------------------------------------------------------------
+ * src/score_based_channels/train_wgan.py:123-184 on the generator above and the critic aux_gan.py:9-56 (DCGAN_D), both in TRAINING mode
+ * (BatchNorm on batch statistics, running statistics updated with momentum 0.1 and the unbiased variance), isize = [16, 64], nz = 60,
+ * nc = 2, ngf = 128, ndf = 64, the same n_extra = 0 .. 4 for both networks, read from the tensor names (csrc/wgan_train.hip):
+ *     D  layer 0: Conv 4 x 4 / 2 2 -> 64, LeakyReLU 0.2;  layers 1 .. n_extra: Conv 3 x 3 64 -> 64, BatchNorm, LeakyReLU;  layer n_extra + 1:
+ *        Conv 4 x 4 / 2 64 -> 128, BatchNorm, LeakyReLU;  layer M = n_extra + 2: Conv (4, 16) 128 -> 1;  mean over the batch.  No bias.
+ *   critic iteration     every parameter of D clamped to [clamp_lower, clamp_upper]; errD_real = mean_b D(real), backward with + 1;
+ *                        fake = G(noise), no gradient through G; errD_fake = mean_b D(fake), backward with - 1, the gradients accumulate;
+ *                        RMSprop on D
+ *   generator iteration  fake = G(noise); errG = mean_b D(fake) (D's running statistics still update, its parameters get no gradient);
+ *                        backward with + 1 through D's input and G's parameters; RMSprop on G; the filters are repacked
+ *   RMSprop              torch.optim.RMSprop's defaults (no momentum, not centred): sq = alpha sq + (1 - alpha) g^2,
+ *                        p = p + (- lr g) / (sqrt(sq) + eps), every operation rounded to fp32
+ * fp32 arithmetic; the generator's 128 -> 128 convolutions run on the fp32 matrix cores in all three directions, the critic on the vector
+ * ALUs; every sum over the batch is taken in float64 in a fixed order; no atomics: a sequence of calls run twice gives the same bits.
+ * All data pointers are DEVICE pointers except where noted.
+ *
+ *   sbc_wgan_trainer_create   copies both networks from HOST float tensors named as in the reference's state_dict()s (the generator's as
+ *                             for sbc_wgan_create; the critic's "main.initial:2-64:conv.weight", "main.extra-layers-<t>:64:conv.weight",
+ *                             "main.extra-layers-<t>:64:batchnorm.{weight,bias,running_mean,running_var}", "main.pyramid:64-128:conv.weight",
+ *                             "main.pyramid:128:batchnorm.*", "main.final:128-1:conv.weight": 7 + 5 n_extra tensors; num_batches_tracked is
+ *                             left out, the caller counts) to the current device; gradients and square averages start at zero.  Every name
+ *                             and element count is checked.  Synchronises.
+ *   sbc_wgan_trainer_workspace_floats   float32 elements of a workspace with a capacity of B_cap samples per batch; -1 on a bad argument.
+ *   sbc_wgan_trainer_critic_step        one critic iteration on real [B_real][2][16][64] and noise [B_fake][60]; losses [2] = errD_real,
+ *                                       errD_fake (or NULL).  Asynchronous on `stream`; every argument is checked before the first launch.
+ *   sbc_wgan_trainer_generator_step     one generator iteration on noise [B][60]; loss [1] = errG (or NULL).
+ *   sbc_wgan_trainer_stage    where a stage of the last call lies in its workspace: `offset` floats from the start; per_sample = 1:
+ *                             [B][channels][height][width] of the batch that wrote it, 0: [channels].  stage = 256 net + 16 kind + layer; net 0
+ *                             the generator (layer k = 0 .. L, 0 the dense output), 1 the critic's pass over real, 2 its pass over fake
+ *                             (layer j = 0 .. M); kind 0 activation, 1 raw convolution output (+ bias), 2 pre-activation, 3 sign mask of the
+ *                             pre-activation as 32-bit words [channels][height][ceil(width / 32)] (bit j of word q: pixel 32 q + j), 4 batch
+ *                             mean, 5 biased batch variance, 6 d loss / d activation, 7 d loss / d raw; net 0: 128 gen, 129 d loss / d gen;
+ *                             net 1, 2: 130 the mean critic output [1].  No stage shares memory with another.
+ *   sbc_wgan_trainer_copy     tensor `name` of net 0 (generator) / 1 (critic) between the device and the HOST array: what = 0 its value (parameters
+ *                             and running statistics), 1 its gradient, 2 its RMSprop square average.  Synchronises the device.
+ *   sbc_wgan_wgrad128, sbc_wgan_bn_backward, sbc_wgan_rmsprop   single launches of the step on the caller's operands:
+ *                             dW [128][128][ks][ks] = sum_{b,y,x} draw[b][co][y][x] in[b][ci][y + ky - p][x + kx - p] (in read through the
+ *                             nearest x 2 map with up = 1; scratch of sbc_wgan_wgrad128_scratch_floats);  the BatchNorm backward of one layer
+ *                             from d loss / d activation (scratch: 2 C floats; dweight = sum dy xhat, dbias = sum dy);  RMSprop (mode 1) or the
+ *                             clamp (mode 0) on n elements. */
+typedef struct sbc_wgan_trainer sbc_wgan_trainer;
+typedef struct sbc_wgan_trainer_desc {
+    double lr_d, lr_g;         /* 5e-5 in the reference                                                                          */
+    double alpha, eps;         /* torch.optim.RMSprop's defaults: 0.99, 1e-8                                                     */
+    double clamp_lower, clamp_upper;   /* -0.01, 0.01                                                                            */
+} sbc_wgan_trainer_desc;
+int sbc_wgan_trainer_create(const sbc_wgan_trainer_desc* desc, const sbc_tensor_ref* gen, int32_t n_gen, const sbc_tensor_ref* disc, int32_t n_disc,
+                            sbc_wgan_trainer** out);
+void sbc_wgan_trainer_destroy(sbc_wgan_trainer* handle);
+int64_t sbc_wgan_trainer_workspace_floats(const sbc_wgan_trainer* handle, int32_t B_cap);
+int sbc_wgan_trainer_critic_step(sbc_wgan_trainer* handle, const float* real, int32_t B_real, const float* noise, int32_t B_fake, float* losses,
+                                 float* workspace, int32_t B_cap, void* stream);
+int sbc_wgan_trainer_generator_step(sbc_wgan_trainer* handle, const float* noise, int32_t B, float* loss, float* workspace, int32_t B_cap, void* stream);
+int sbc_wgan_trainer_stage(const sbc_wgan_trainer* handle, int32_t stage, int32_t B_cap, int64_t* offset, int32_t* channels, int32_t* height,
+                           int32_t* width, int32_t* per_sample);
+int sbc_wgan_trainer_copy(sbc_wgan_trainer* handle, int32_t net, int32_t what, const char* name, float* host, int64_t numel, int32_t to_device);
+int64_t sbc_wgan_wgrad128_scratch_floats(int32_t B, int32_t H, int32_t W, int32_t ks);
+int sbc_wgan_wgrad128(const float* draw, const float* in, float* dW, float* scratch, int32_t B, int32_t H, int32_t W, int32_t ks, int32_t up,
+                      void* stream);
+int sbc_wgan_bn_backward(const float* gact, const float* raw, const int32_t* mask, const float* mean, const float* var, const float* weight, float slope,
+                         float* draw, float* dweight, float* dbias, float* scratch, int32_t B, int32_t C, int32_t H, int32_t W, void* stream);
+int sbc_wgan_rmsprop(float* p, const float* g, float* sq, int64_t n, double lr, double alpha, double eps, double clamp_lower, double clamp_upper,
+                     int32_t mode, void* stream);
 
 /* ---- Environment variables -------------------------------------------------------------------------------------------------
  * Everything the library (csrc/) and the Python host (score_based_channels_amd/) read from the environment, in ONE place.  None of them

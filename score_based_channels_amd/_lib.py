@@ -21,7 +21,10 @@ EXPORTS = ('sbc_abi_version', 'sbc_set_persistent_cus', 'sbc_last_error', 'sbc_d
            'sbc_score_destroy', 'sbc_wgrad_scratch_floats', 'sbc_l1_lifted_run', 'sbc_ls_regularized',
            'sbc_ldamp_create', 'sbc_ldamp_destroy', 'sbc_ldamp_workspace_floats', 'sbc_ldamp_denoise', 'sbc_ldamp_run', 'sbc_ldamp_stage',
            'sbc_debug_ldamp_directions',
-           'sbc_wgan_create', 'sbc_wgan_destroy', 'sbc_wgan_workspace_floats', 'sbc_wgan_generate', 'sbc_wgan_run', 'sbc_wgan_stage')
+           'sbc_wgan_create', 'sbc_wgan_destroy', 'sbc_wgan_workspace_floats', 'sbc_wgan_generate', 'sbc_wgan_run', 'sbc_wgan_stage',
+           'sbc_wgan_trainer_create', 'sbc_wgan_trainer_destroy', 'sbc_wgan_trainer_workspace_floats', 'sbc_wgan_trainer_critic_step',
+           'sbc_wgan_trainer_generator_step', 'sbc_wgan_trainer_stage', 'sbc_wgan_trainer_copy', 'sbc_wgan_wgrad128_scratch_floats',
+           'sbc_wgan_wgrad128', 'sbc_wgan_bn_backward', 'sbc_wgan_rmsprop')
 
 
 class SbcError(RuntimeError):
@@ -116,6 +119,12 @@ class sbc_wgan_run_desc(C.Structure):
                 ('B', C.c_int32), ('Np', C.c_int32), ('first_step', C.c_int32), ('n_steps', C.c_int32)]
 
 
+# WGAN training (wgan.Trainer)
+class sbc_wgan_trainer_desc(C.Structure):
+    _fields_ = [('lr_d', C.c_double), ('lr_g', C.c_double), ('alpha', C.c_double), ('eps', C.c_double), ('clamp_lower', C.c_double),
+                ('clamp_upper', C.c_double)]
+
+
 _lib = None
 
 
@@ -182,6 +191,21 @@ def lib():
     h.sbc_wgan_run.argtypes = [C.c_void_p, C.POINTER(sbc_wgan_run_desc), C.c_void_p]
     h.sbc_wgan_stage.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                  C.POINTER(C.c_int32)]
+    h.sbc_wgan_trainer_create.argtypes = [C.POINTER(sbc_wgan_trainer_desc), C.POINTER(sbc_tensor_ref), C.c_int32, C.POINTER(sbc_tensor_ref), C.c_int32,
+                                          C.POINTER(C.c_void_p)]
+    h.sbc_wgan_trainer_destroy.argtypes = [C.c_void_p]
+    h.sbc_wgan_trainer_destroy.restype = None
+    h.sbc_wgan_trainer_workspace_floats.argtypes = [C.c_void_p, C.c_int32]
+    h.sbc_wgan_trainer_workspace_floats.restype = C.c_int64
+    h.sbc_wgan_trainer_critic_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    h.sbc_wgan_trainer_generator_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    h.sbc_wgan_trainer_stage.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 4
+    h.sbc_wgan_trainer_copy.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_void_p, C.c_int64, C.c_int32]
+    h.sbc_wgan_wgrad128_scratch_floats.argtypes = [C.c_int32] * 4
+    h.sbc_wgan_wgrad128_scratch_floats.restype = C.c_int64
+    h.sbc_wgan_wgrad128.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]
+    h.sbc_wgan_bn_backward.argtypes = [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]
+    h.sbc_wgan_rmsprop.argtypes = [C.c_void_p] * 3 + [C.c_int64] + [C.c_double] * 5 + [C.c_int32, C.c_void_p]
     if h.sbc_abi_version() != ABI_VERSION:
         raise SbcError('libsbc_hip.so ABI %d != expected %d' % (h.sbc_abi_version(), ABI_VERSION))
     _lib = h

@@ -23,6 +23,7 @@
 // Every stage of the last call stays readable in the caller's workspace (sbc_wgan_stage); no stage shares memory with another.
 #include "common.h"
 #include "host_params.h"
+#include "wgan_shared.h"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -113,8 +114,13 @@ struct ConvCfg {
     static_assert((IN_FLOATS + W_FLOATS) * 4 <= 64 * 1024 && W_FLOATS % 4 == 0 && CH % CC == 0 && CC % 2 == 0, "tiling");
 };
 
-template <int KS>
+// RAW (training, wgan_train.hip): the prologue applies no mask and no scale -- in training the incoming gradient is already complete --
+// and the epilogue writes the convolution (+ bias where there is one) and nothing else, or its 2 x 2 block sums with `pool`.
+// The template argument is KS, + 100 for RAW: the existing instantiations keep their symbols and their code.
+template <int KSM>
 __global__ __launch_bounds__(256) void conv128_kernel(ConvArgs a) {
+    constexpr int KS = KSM % 100;
+    constexpr bool RAW = KSM >= 100;
     using K = ConvCfg<KS>;
     __shared__ __align__(16) float w_s[K::W_FLOATS];
     __shared__ float in_s[K::IN_FLOATS];
@@ -124,7 +130,7 @@ __global__ __launch_bounds__(256) void conv128_kernel(ConvArgs a) {
     const int H = a.H, W = a.W, up = a.up, Hs = H >> up, Ws = W >> up, MW = W >> 5;
     const bool bwd = a.bwd != 0;
     const float* src = a.src + (size_t)n * CH * Hs * Ws;
-    const uint32_t* mk = bwd ? a.mask_in + (size_t)n * CH * H * MW : nullptr;
+    const uint32_t* mk = (!RAW && bwd) ? a.mask_in + (size_t)n * CH * H * MW : nullptr;
 
     // where this thread's positions of the input tile (the same in every channel and chunk) lie in the source plane and in the mask
     // words; -1: zero padding
@@ -169,10 +175,11 @@ __global__ __launch_bounds__(256) void conv128_kernel(ConvArgs a) {
                     float v = 0.f;
                     if (soff[i] >= 0) {
                         v = src[(size_t)cg * Hs * Ws + soff[i]];
-                        if (bwd) {
-                            const uint32_t m = mk[(size_t)cg * H * MW + moff[i]];
-                            v = ((m >> shift[i]) & 1u) ? v * a.scale_in[cg] : 0.f;
-                        }
+                        if constexpr (!RAW)
+                            if (bwd) {
+                                const uint32_t m = mk[(size_t)cg * H * MW + moff[i]];
+                                v = ((m >> shift[i]) & 1u) ? v * a.scale_in[cg] : 0.f;
+                            }
                     }
                     in_s[ci * K::PLANE + p] = v;
                 }
@@ -204,6 +211,22 @@ __global__ __launch_bounds__(256) void conv128_kernel(ConvArgs a) {
 
     // D layout: channel (row) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the block, pixel (column) = lane & 31
     const int x = x0 + l31;
+    if constexpr (RAW) {
+        // the convolution (+ bias) and nothing else; with `pool` (the launcher sets bwd with it) the pooled epilogue below
+        if (!a.pool) {
+            float* out = a.out + (size_t)n * CH * H * W;
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int c = wn * 64 + nb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                    const float bias = a.bias ? a.bias[c] : 0.f;
+#pragma unroll
+                    for (int mb = 0; mb < 2; ++mb) out[((size_t)c * H + y0 + 2 * wm + mb) * W + x] = a.bias ? acc[mb][nb][r] + bias : acc[mb][nb][r];
+                }
+            return;
+        }
+    }
     if (!bwd) {
         float* out = a.out + (size_t)n * CH * H * W;
         uint32_t* mo = a.mask_out + (size_t)n * CH * H * MW;
@@ -249,6 +272,17 @@ __global__ __launch_bounds__(256) void conv128_kernel(ConvArgs a) {
                 if ((lane & 1) == 0) out[((size_t)c * Hp + (y0 >> 1) + wm) * Wp + (x >> 1)] = h0 + h1;
             }
     }
+}
+
+// ---- filters of one layer from the torch layout into the two packings of conv128 (pack_conv below, on the device) ----------------
+// training repacks after every generator update; grid (CH * CH * KS^2 / 256), thread e = one element of the torch tensor [co][ci][tap]
+__global__ __launch_bounds__(256) void repack128_kernel(const float* __restrict__ w, float* __restrict__ fwd, float* __restrict__ adj, int T, int CC) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= CH * CH * T) return;
+    const int co = e / (CH * T), ci = (e / T) % CH, t = e % T;
+    const float v = w[e];
+    fwd[(((size_t)(ci / CC) * T + t) * CC + ci % CC) * CH + co] = v;
+    adj[(((size_t)(co / CC) * T + (T - 1 - t)) * CC + co % CC) * CH + ci] = v;
 }
 
 // ---- out: 5 x 5 convolution 128 -> 2 + bias; R = G P - Y; meas; oracle NMSE; dG = 2 s R P^H --------------------------------------
@@ -509,6 +543,39 @@ struct Layout {
 enum { ST_ACT = 0, ST_GEN = 16, ST_DG = 17, ST_GRAD = 32, ST_MASK = 48 };
 
 }  // namespace
+
+// ---- what training launches of this file (wgan_shared.h) --------------------------------------------------------------------------------
+namespace wgan_shared {
+static_assert(NR == sbc::NR && NT == sbc::NT && NZ == sbc::NZ && CH == sbc::CH && MAX_EXTRA == sbc::MAX_EXTRA, "one geometry");
+
+void launch_dense(const float* z, const float* W, const float* bias, float* out, int B, hipStream_t s) {
+    hipLaunchKernelGGL(dense_kernel, dim3(DENSE / 256, B), dim3(256), 0, s, z, W, bias, out);
+}
+
+void launch_conv128_raw(const float* src, const float* wpk, const float* bias, float* out, int H, int W, int ks, int up, int pool, int B, hipStream_t s) {
+    ConvArgs a{};
+    a.src = src; a.wpk = wpk; a.bias = bias; a.out = out; a.H = H; a.W = W; a.up = up; a.pool = pool; a.bwd = pool;
+    const dim3 grid(W / 32, H / 4, B);
+    if (ks == 5) hipLaunchKernelGGL(conv128_kernel<105>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(conv128_kernel<103>, grid, dim3(256), 0, s, a);
+}
+
+void launch_out_conv(const float* act, const float* w, const float* bias, float* gen, int B, hipStream_t s) {
+    OutArgs oa{};
+    oa.act = act; oa.w = w; oa.bias = bias; oa.gen = gen;
+    hipLaunchKernelGGL(out_kernel, dim3(B), dim3(256), 0, s, oa);
+}
+
+void launch_out_adjoint(const float* dG, const float* w, float* out, int B, hipStream_t s) {
+    hipLaunchKernelGGL(out_adjoint_kernel, dim3(CH / OA_CG, B), dim3(256), 0, s, dG, w, out);
+}
+
+void launch_repack128(const float* w, float* fwd, float* adj, int ks, hipStream_t s) {
+    const int T = ks * ks;
+    hipLaunchKernelGGL(repack128_kernel, dim3(CH * CH * T / 256), dim3(256), 0, s, w, fwd, adj, T, ks == 5 ? ConvCfg<5>::CC : ConvCfg<3>::CC);
+}
+
+}  // namespace wgan_shared
 }  // namespace sbc
 
 struct sbc_wgan {
@@ -562,6 +629,7 @@ void forward(const sbc_wgan* h, const Ws& ws, const float* z, hipStream_t s) {
 }
 
 }  // namespace
+
 }  // namespace sbc
 
 extern "C" {

@@ -5,6 +5,10 @@
 Supported is the one geometry the reference module's literal ``hidden.view(-1, 128, Nr // 4, Nt // 4)`` admits: ``isize = [16, 64]``
 (Nr, Nt), ``nz = 60``, ``nc = 2``, ``ngf = 128``, 0 .. 4 extra layers.  Anything else raises ``ValueError`` on the host.
 
+The second half of the module is the training of that generator (``train_wgan.py:96-202``): the critic ``aux_gan.DCGAN_D``'s state-dict
+surface, the reference's initial distributions and ``Trainer`` with its critic and generator iterations (``csrc/wgan_train.hip`` behind
+``sbc_wgan_trainer_*``).
+
 torch only owns the device memory and the stream; every number is computed by the HIP kernels (``csrc/wgan.hip`` behind ``sbc_wgan_*``
 of ``include/sbc_hip.h``).  ``state_dict_spec`` / ``seeded_state_dict`` / ``check_*`` need neither torch nor the library.
 """
@@ -287,3 +291,298 @@ class LatentOptimizer:
                 t.record_stream(torch.cuda.current_stream(dev))
         G.last_workspace = (ws, B)
         return z, {'m': m, 'v': v, 'step': first - 1 + steps}, logs
+
+
+# ---- WGAN training (train_wgan.py:96-202 on csrc/wgan_train.hip behind sbc_wgan_trainer_*) ---------------------------------------------
+NDF = 64
+_KINDS = {'act': 0, 'raw': 1, 'pre': 2, 'mask': 3, 'mean': 4, 'var': 5, 'gact': 6, 'draw': 7}
+_NETS = {'g': 0, 'd0': 1, 'd1': 2}                     # the generator; the critic's pass over real; its pass over fake
+RMSPROP_DEFAULTS = dict(lr=5e-5, alpha=0.99, eps=1e-8)
+CLAMP = (-0.01, 0.01)
+
+
+def _disc_bn_spec(prefix, c):
+    return [(prefix + '.weight', (c,)), (prefix + '.bias', (c,)), (prefix + '.running_mean', (c,)), (prefix + '.running_var', (c,)),
+            (prefix + '.num_batches_tracked', ())]
+
+
+def disc_state_dict_spec(n_extra=1):
+    """Ordered ``[(name, shape)]`` of the reference ``DCGAN_D(isize=[16, 64], nz=60, nc=2, ndf=64, ngpu=1, n_extra_layers=n_extra)``'s
+    ``state_dict()`` (``aux_gan.py:9-47``; no convolution has a bias)."""
+    n_extra = int(n_extra)
+    if not 0 <= n_extra <= MAX_EXTRA:
+        raise ValueError('n_extra must be in [0, %d] (got %r)' % (MAX_EXTRA, n_extra))
+    t = [('main.initial:%d-%d:conv.weight' % (NC, NDF), (NDF, NC, 4, 4))]
+    for i in range(n_extra):
+        t += [('main.extra-layers-%d:%d:conv.weight' % (i, NDF), (NDF, NDF, 3, 3))] + _disc_bn_spec('main.extra-layers-%d:%d:batchnorm' % (i, NDF), NDF)
+    t += [('main.pyramid:%d-%d:conv.weight' % (NDF, 2 * NDF), (2 * NDF, NDF, 4, 4))] + _disc_bn_spec('main.pyramid:%d:batchnorm' % (2 * NDF), 2 * NDF)
+    return t + [('main.final:%d-1:conv.weight' % (2 * NDF), (1, 2 * NDF, NR // 4, NT // 4))]
+
+
+def check_disc_geometry(isize, nz, nc, ndf, n_extra_layers=0):
+    isize = [int(v) for v in isize]
+    if isize != [NR, NT] or int(nz) != NZ or int(nc) != NC or int(ndf) != NDF:
+        raise ValueError('only isize = [%d, %d], nz = %d, nc = %d, ndf = %d is supported (got isize %s, nz %s, nc %s, ndf %s)'
+                         % (NR, NT, NZ, NC, NDF, isize, nz, nc, ndf))
+    if not 0 <= int(n_extra_layers) <= MAX_EXTRA:
+        raise ValueError('n_extra_layers must be in [0, %d] (got %r)' % (MAX_EXTRA, n_extra_layers))
+    return int(n_extra_layers)
+
+
+def init_state_dicts(seed, n_extra=1):
+    """``(gen_state, disc_state)`` drawn as ``train_wgan.py:78-94`` initialises them: convolution weights N(0, 0.02), BatchNorm weights
+    N(1, 0.02) and biases 0, running statistics (0, 1, 0 batches); the dense layer and the convolution biases, which ``weights_init`` does
+    not touch, keep torch's default U(-1 / sqrt(fan_in), 1 / sqrt(fan_in)).  A tensor's values depend on the seed and its own name only
+    (numpy ``PCG64`` keyed by ``(seed, crc32(name))``, like ``seeded_state_dict``)."""
+    out = []
+    for spec in (state_dict_spec(n_extra), disc_state_dict_spec(n_extra)):
+        sd = {}
+        for name, shape in spec:
+            rng = np.random.Generator(np.random.PCG64([int(seed), zlib.crc32(name.encode())]))
+            leaf = name.rsplit('.', 1)[1]
+            is_bn = '.bn' in name or '_bn' in name or 'batchnorm' in name
+            if leaf == 'num_batches_tracked':
+                sd[name] = np.asarray(0, np.int64)
+                continue
+            if is_bn:
+                v = {'weight': lambda: 1.0 + 0.02 * rng.standard_normal(shape), 'bias': lambda: np.zeros(shape),
+                     'running_mean': lambda: np.zeros(shape), 'running_var': lambda: np.ones(shape)}[leaf]()
+            elif name.startswith('dense.') or leaf == 'bias':
+                fan_in = NZ if name.startswith('dense.') else NGF * 25
+                v = rng.uniform(-1.0, 1.0, size=shape) / np.sqrt(fan_in)
+            else:
+                v = 0.02 * rng.standard_normal(shape)
+            sd[name] = np.asarray(v, np.float32)
+        out.append(sd)
+    return tuple(out)
+
+
+class DCGAN_D:
+    """``DCGAN_D(isize, nz, nc, ndf, ngpu, n_extra_layers)`` with the reference module's ``state_dict`` surface: the critic exists on the
+    device inside a ``Trainer`` only, so this object holds its tensors on the host (numpy) and checks names and shapes."""
+
+    def __init__(self, isize, nz, nc, ndf, ngpu=1, n_extra_layers=0):
+        self.n_extra = check_disc_geometry(isize, nz, nc, ndf, n_extra_layers)
+        self.ngpu = ngpu
+        self._sd = None
+
+    def load_state_dict(self, state):
+        sd = _lib.numpy_state_dict(state)
+        _lib.check_against_spec(sd, disc_state_dict_spec(self.n_extra))
+        self._sd = {n: np.array(sd[n]) for n, _ in disc_state_dict_spec(self.n_extra)}
+        return self
+
+    def state_dict(self):
+        if self._sd is None:
+            raise RuntimeError('DCGAN_D has no weights: call load_state_dict first')
+        return dict(self._sd)
+
+
+def trainer_stage_id(name, n_extra):
+    """``'<net>.<kind><layer>'``: net ``g`` (layer 0 .. L, 0 the dense output), ``d0`` / ``d1`` the critic's pass over real / fake (layer
+    0 .. M = n_extra + 2); kind ``act raw pre mask mean var gact`` (d loss / d activation) ``draw`` (d loss / d raw); and ``g.gen``,
+    ``g.dgen``, ``d0.err``, ``d1.err``."""
+    net, _, rest = name.partition('.')
+    if net in _NETS:
+        special = {('g', 'gen'): 128, ('g', 'dgen'): 129, ('d0', 'err'): 130, ('d1', 'err'): 130}
+        if (net, rest) in special:
+            return 256 * _NETS[net] + special[(net, rest)]
+        for kind, q in _KINDS.items():
+            if rest.startswith(kind) and rest[len(kind):].isdigit() and int(rest[len(kind):]) <= (2 + n_extra if net == 'g' else n_extra + 2):
+                return 256 * _NETS[net] + 16 * q + int(rest[len(kind):])
+    raise ValueError('no stage %r in networks with %d extra layers' % (name, n_extra))
+
+
+class Trainer(_lib.DeviceHandle):
+    """Both networks of ``train_wgan.py`` in training mode on the device, with their RMSprop states.
+
+    ``Trainer(gen_state, disc_state, batch_size=200)``; ``critic_step(real [Br, 2, 16, 64], noise [Bf, 60])`` -> float32 ``[2]`` on the
+    device (``errD_real``, ``errD_fake``); ``generator_step(noise [B, 60])`` -> ``[1]`` (``errG``); ``state_dicts()`` and
+    ``optimizer_state_dicts()`` (``torch.optim.RMSprop.state_dict()`` form) as numpy on the host; ``stage(name)`` a view of the last
+    call's workspace (``trainer_stage_id``); ``tensor(net, name, what)`` / ``set_tensor`` a parameter, its gradient or its square average."""
+
+    _destroy = 'sbc_wgan_trainer_destroy'
+
+    def __init__(self, gen_state, disc_state, batch_size=200, lrD=5e-5, lrG=5e-5, alpha=0.99, eps=1e-8, clamp=CLAMP, device=None):
+        super().__init__(device)
+        import torch
+        gsd, dsd = _lib.numpy_state_dict(gen_state), _lib.numpy_state_dict(disc_state)
+        self.n_extra = n_extra_of(gsd)
+        if not 0 <= self.n_extra <= MAX_EXTRA:
+            raise ValueError('at most %d extra layers are supported (got %d)' % (MAX_EXTRA, self.n_extra))
+        check_state_dict(gsd, self.n_extra)
+        _lib.check_against_spec(dsd, disc_state_dict_spec(self.n_extra))
+        if int(batch_size) < 1 or int(batch_size) > 32768:
+            raise ValueError('batch_size must be in [1, 32768] (got %r)' % (batch_size,))
+        self.capacity = int(batch_size)
+        self.hyper = dict(lrD=float(lrD), lrG=float(lrG), alpha=float(alpha), eps=float(eps), clamp=(float(clamp[0]), float(clamp[1])))
+        self._names = [[n for n, _ in spec if not n.endswith('num_batches_tracked')] for spec in (state_dict_spec(self.n_extra), disc_state_dict_spec(self.n_extra))]
+        self._shapes = [dict(state_dict_spec(self.n_extra)), dict(disc_state_dict_spec(self.n_extra))]
+        self._tracked = [int(next(v for k, v in sd.items() if k.endswith('num_batches_tracked'))) for sd in (gsd, dsd)]
+        self.steps = [0, 0]                              # optimiser steps taken: generator, critic
+        desc = _lib.sbc_wgan_trainer_desc(self.hyper['lrD'], self.hyper['lrG'], self.hyper['alpha'], self.hyper['eps'], *self.hyper['clamp'])
+        grefs, gkeep = _lib.tensor_refs(gsd, self._names[0])
+        drefs, dkeep = _lib.tensor_refs(dsd, self._names[1])
+        handle = C.c_void_p()
+        with torch.cuda.device(self._torch_device()):
+            _lib.check(_lib.lib().sbc_wgan_trainer_create(C.byref(desc), grefs, len(grefs), drefs, len(drefs), C.byref(handle)))
+        self._h = handle
+        self.last_batch = {}
+
+    def _prepare(self, stream):
+        import torch
+        dev = self._torch_device()
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):
+            ws = self._workspace_of(_lib.lib().sbc_wgan_trainer_workspace_floats(self._h, self.capacity), dev)
+        return dev, s, ws
+
+    def _input(self, x, shape, name, dev, s):
+        import torch
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        if x.dim() == 4 and len(shape) == 1 and tuple(x.shape[2:]) == (1, 1):
+            x = x[:, :, 0, 0]
+        if x.dim() != 1 + len(shape) or tuple(x.shape[1:]) != shape:
+            raise ValueError('%s must be [B, %s] (got %s)' % (name, ', '.join(map(str, shape)), tuple(x.shape)))
+        if not 1 <= x.shape[0] <= self.capacity:
+            raise ValueError('%s: a batch must hold 1 .. %d samples, the trainer\'s batch_size (got %d)' % (name, self.capacity, x.shape[0]))
+        with torch.cuda.device(dev), torch.cuda.stream(s):
+            return x.detach().to(dev, torch.float32).contiguous()
+
+    def critic_step(self, real, noise, stream=None):
+        import torch
+        dev, s, ws = self._prepare(stream)
+        real, noise = self._input(real, (NC, NR, NT), 'real', dev, s), self._input(noise, (NZ,), 'noise', dev, s)
+        with torch.cuda.device(dev):
+            with torch.cuda.stream(s):
+                out = torch.empty(2, dtype=torch.float32, device=dev)
+            _lib.check(_lib.lib().sbc_wgan_trainer_critic_step(self._h, C.c_void_p(real.data_ptr()), real.shape[0], C.c_void_p(noise.data_ptr()),
+                                                               noise.shape[0], C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), self.capacity,
+                                                               C.c_void_p(s.cuda_stream)))
+            for t in (real, noise, ws, out):
+                t.record_stream(s)
+            out.record_stream(torch.cuda.current_stream(dev))
+        self._tracked[0] += 1
+        self._tracked[1] += 2
+        self.steps[1] += 1
+        self.last_batch = {'g': noise.shape[0], 'd0': real.shape[0], 'd1': noise.shape[0]}
+        return out
+
+    def generator_step(self, noise, stream=None):
+        import torch
+        dev, s, ws = self._prepare(stream)
+        noise = self._input(noise, (NZ,), 'noise', dev, s)
+        with torch.cuda.device(dev):
+            with torch.cuda.stream(s):
+                out = torch.empty(1, dtype=torch.float32, device=dev)
+            _lib.check(_lib.lib().sbc_wgan_trainer_generator_step(self._h, C.c_void_p(noise.data_ptr()), noise.shape[0], C.c_void_p(out.data_ptr()),
+                                                                  C.c_void_p(ws.data_ptr()), self.capacity, C.c_void_p(s.cuda_stream)))
+            for t in (noise, ws, out):
+                t.record_stream(s)
+            out.record_stream(torch.cuda.current_stream(dev))
+        self._tracked[0] += 1
+        self._tracked[1] += 1
+        self.steps[0] += 1
+        self.last_batch.update({'g': noise.shape[0], 'd1': noise.shape[0]})
+        return out
+
+    def stage(self, name):
+        """A stage of the last call as a view of the workspace: ``[B, C, H, W]`` of the batch that wrote it, ``[C]`` for ``mean`` / ``var`` /
+        ``err``; masks as int32 words (``unpack_mask``)."""
+        import torch
+        off, c, h, w, per = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        _lib.check(_lib.lib().sbc_wgan_trainer_stage(self._h, trainer_stage_id(name, self.n_extra), self.capacity, C.byref(off), C.byref(c),
+                                                     C.byref(h), C.byref(w), C.byref(per)))
+        if not per.value:
+            return self._ws[off.value:off.value + c.value]
+        B = self.last_batch[name.partition('.')[0]]
+        t = self._ws[off.value:off.value + B * c.value * h.value * w.value]
+        if '.mask' in name:
+            t = t.view(torch.int32)
+        return t.view(B, c.value, h.value, w.value)
+
+    def _copy(self, net, name, what, arr, to_device):
+        import torch
+        net_i, what_i = {'g': 0, 'd': 1}[net], {'value': 0, 'grad': 1, 'square_avg': 2}[what]
+        with torch.cuda.device(self._torch_device()):
+            _lib.check(_lib.lib().sbc_wgan_trainer_copy(self._h, net_i, what_i, name.encode(), arr.ctypes.data_as(C.c_void_p), arr.size, int(to_device)))
+
+    def tensor(self, net, name, what='value'):
+        """Tensor ``name`` of net ``'g'`` / ``'d'`` as a numpy array: its ``'value'``, ``'grad'`` or ``'square_avg'``.  Waits for the device."""
+        arr = np.empty(self._shapes[{'g': 0, 'd': 1}[net]][name], np.float32)
+        self._copy(net, name, what, arr, False)
+        return arr
+
+    def set_tensor(self, net, name, value, what='value'):
+        arr = np.ascontiguousarray(value, np.float32)
+        if arr.shape != tuple(self._shapes[{'g': 0, 'd': 1}[net]][name]):
+            raise ValueError('size mismatch for %s: %s vs %s' % (name, arr.shape, self._shapes[{'g': 0, 'd': 1}[net]][name]))
+        self._copy(net, name, what, arr, True)
+
+    def parameter_names(self, net):
+        """The trainable tensors in ``parameters()`` order"""
+        return [n for n in self._names[{'g': 0, 'd': 1}[net]] if not n.endswith(('running_mean', 'running_var'))]
+
+    def state_dicts(self):
+        out = []
+        for i, net in enumerate('gd'):
+            sd = {}
+            for n, _ in (state_dict_spec, disc_state_dict_spec)[i](self.n_extra):
+                sd[n] = np.asarray(self._tracked[i], np.int64) if n.endswith('num_batches_tracked') else self.tensor(net, n)
+            out.append(sd)
+        return tuple(out)
+
+    def optimizer_state_dicts(self):
+        """``(gen_opt_state, disc_opt_state)`` as ``torch.optim.RMSprop(...).state_dict()`` lays them out (numpy in place of tensors)"""
+        out = []
+        for i, net in enumerate('gd'):
+            names = self.parameter_names(net)
+            state = {}
+            if self.steps[i]:
+                state = {k: {'step': np.asarray(float(self.steps[i]), np.float32), 'square_avg': self.tensor(net, n, 'square_avg')} for k, n in enumerate(names)}
+            group = dict(lr=self.hyper['lrG' if net == 'g' else 'lrD'], momentum=0, alpha=self.hyper['alpha'], eps=self.hyper['eps'], centered=False,
+                         weight_decay=0, capturable=False, foreach=None, maximize=False, differentiable=False, params=list(range(len(names))))
+            out.append({'state': state, 'param_groups': [group]})
+        return tuple(out)
+
+
+def bn_backward(gact, raw, mask_words, mean, var, weight, slope):
+    """One BatchNorm backward (``sbc_wgan_bn_backward``) on device tensors -> ``(draw, dweight, dbias)``"""
+    import torch
+    B, Cn, H, W = gact.shape
+    draw, dw, db = torch.empty_like(gact), torch.empty(Cn, dtype=torch.float32, device=gact.device), torch.empty(Cn, dtype=torch.float32, device=gact.device)
+    scratch = torch.empty(2 * Cn, dtype=torch.float32, device=gact.device)
+    p = lambda t: C.c_void_p(t.data_ptr())           # noqa: E731
+    s = torch.cuda.current_stream(gact.device)
+    with torch.cuda.device(gact.device):
+        _lib.check(_lib.lib().sbc_wgan_bn_backward(p(gact), p(raw), p(mask_words), p(mean), p(var), p(weight), float(slope), p(draw), p(dw), p(db),
+                                                   p(scratch), B, Cn, H, W, C.c_void_p(s.cuda_stream)))
+    return draw, dw, db
+
+
+def wgrad128(draw, inp, ks, up):
+    """``sbc_wgan_wgrad128`` on device tensors: draw ``[B, 128, H, W]``, inp ``[B, 128, H >> up, W >> up]`` -> ``[128, 128, ks, ks]``"""
+    import torch
+    B, _, H, W = draw.shape
+    n = _lib.lib().sbc_wgan_wgrad128_scratch_floats(B, H, W, int(ks))
+    if n < 0:
+        raise ValueError('wgrad128: unsupported shape %s, ks %r' % (tuple(draw.shape), ks))
+    scratch = torch.empty(n, dtype=torch.float32, device=draw.device)
+    dW = torch.empty((NGF, NGF, ks, ks), dtype=torch.float32, device=draw.device)
+    s = torch.cuda.current_stream(draw.device)
+    with torch.cuda.device(draw.device):
+        _lib.check(_lib.lib().sbc_wgan_wgrad128(C.c_void_p(draw.data_ptr()), C.c_void_p(inp.data_ptr()), C.c_void_p(dW.data_ptr()),
+                                                C.c_void_p(scratch.data_ptr()), B, H, W, int(ks), int(up), C.c_void_p(s.cuda_stream)))
+    return dW
+
+
+def rmsprop(p, g, sq, lr=5e-5, alpha=0.99, eps=1e-8, clamp=None, stream=None):
+    """``sbc_wgan_rmsprop`` in place on flat float32 device tensors: one RMSprop step, or with ``clamp=(lo, hi)`` the clamp alone"""
+    import torch
+    s = stream if stream is not None else torch.cuda.current_stream(p.device)
+    lo, hi = clamp if clamp is not None else (0.0, 0.0)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None           # noqa: E731
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().sbc_wgan_rmsprop(ptr(p), ptr(g), ptr(sq), p.numel(), float(lr), float(alpha), float(eps), float(lo), float(hi),
+                                               0 if clamp is not None else 1, C.c_void_p(s.cuda_stream)))

@@ -4,6 +4,9 @@
     python tools/kernel_coverage.py                         check the built library against profiles/kernel_coverage.txt (exit 1 on a hole)
     python tools/kernel_coverage.py STATS.csv [...]         table + never-launched list for these rocprofv3 kernel-statistics files
     python tools/kernel_coverage.py --write STATS.csv [...] the same, and rewrite the record from them
+    python tools/kernel_coverage.py --write --merge STATS.csv [...]   rewrite the record from these files AND its current launched set: for
+                                                            a change that leaves the other modules' kernels identical (tools/device_code_diff.py),
+                                                            only the modules that launch the new kernels are traced again
     options:  --lib PATH  --record PATH  --parent-lib PATH --parent STATS.csv [...]  (the suite of the parent commit, for the first table;
               without them --write carries the record's current table over as the parent's)  --bench FILE [...]  (benchmark traces to list)
 
@@ -40,6 +43,12 @@ rocprofv3 --kernel-trace --stats -M -f csv -d <dir>/M -- python -m pytest tests/
     --deselect tests/test_gpu_train.py::test_data_parallel_training_is_the_same_optimisation
 # (the deselected tests start ranks through torch.distributed.run: the same kernels as the single-process tests, more processes)
 python tools/kernel_coverage.py --write <dir>"""
+
+
+MERGED = """\
+# THIS record was written with --write --merge: its launched set is the previous record's set plus the kernels in traces of only the
+# modules that launch new kernels, taken with the command above; every kernel both libraries hold was shown to be identical
+# (tools/device_code_diff.py).  A kernel whose code changes must be traced again, not carried over.  Traces merged in:"""
 
 
 def library_kernels(path):
@@ -193,6 +202,7 @@ def main():
     ap.add_argument('--lib', default=LIB)
     ap.add_argument('--record', default=RECORD)
     ap.add_argument('--write', action='store_true')
+    ap.add_argument('--merge', action='store_true')
     ap.add_argument('--parent', nargs='*', default=[])
     ap.add_argument('--parent-lib')
     ap.add_argument('--parent-title', default='parent commit')
@@ -202,6 +212,8 @@ def main():
         return check(a.lib, a.record)
     lib = library_kernels(a.lib)
     launched = launched_kernels(a.stats)
+    if a.merge:
+        launched |= record_sets(a.record)[0]
     dem = demangle(lib)
     tab = table(lib, launched, dem)
     never = sorted(lib - launched, key=lambda n: dem[n])
@@ -224,7 +236,7 @@ def main():
         ptab = [ln for ln in old.get('TABLE this suite', []) if ln.strip()]
     out = ['Kernel coverage of the GPU suite: which kernels of libsbc_hip.so a comparison test launches.  Written and checked by',
            'tools/kernel_coverage.py; tests/test_kernel_coverage_cpu.py holds every later build to it.  1x MI355X.', '',
-           '== COMMANDS'] + COMMANDS.splitlines() + ['', '== TABLE ' + a.parent_title] + ptab + ['', '== TABLE this suite'] + tab
+           '== COMMANDS'] + COMMANDS.splitlines() + (MERGED.splitlines() + ['#   ' + (os.path.relpath(f, d) if os.path.isdir(d) else os.path.basename(f)) for d in a.stats for f in stats_files([d])] if a.merge else []) + ['', '== TABLE ' + a.parent_title] + ptab + ['', '== TABLE this suite'] + tab
     out += ['', '== BENCHMARK KERNELS'] + bench
     out += ['', '== NOT LAUNCHED', '# one line per kernel: mangled name, a blank, the reason']
     out += ['%s %s' % (n, waived.get(n, '')) for n in never]
