@@ -19,6 +19,7 @@
 // At L = 4 that is 4 x 262144 + 65536 CMAC = 8 x 1114112 real FLOP = 8.91 MFLOP per problem-step.
 // Every sum has a fixed order and no problem reads another's data: a problem's result does not depend on the batch.
 #include "common.h"
+#include "reduce.h"
 #include <math.h>
 #include <map>
 #include <mutex>
@@ -34,11 +35,6 @@ constexpr int GS = L1_NT + 1;              // padded row stride of G (float2): t
 constexpr int US = L1_NR + 1;              // padded row stride of U and T
 
 __device__ __forceinline__ f4 mfma(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);     // butterfly: every lane ends with the same bits
-    return v;
-}
 
 template <int L>
 struct Geo {

@@ -22,6 +22,14 @@ public:
         }
         return SBC_OK;
     }
+    // build() for a state dict that must name every tensor once: `what` is the message's noun ("tensor", "critic tensor")
+    int build_unique(const char* who, const char* what, const sbc_tensor_ref* tensors, int n) {
+        const char* twice = nullptr;
+        const int rc = build(who, tensors, n, &twice);
+        if (rc) return rc;
+        SBC_REQUIRE(!twice, "%s: %s '%s' given twice", who, what, twice);
+        return SBC_OK;
+    }
     bool has(const std::string& name) const { return by_name_.count(name) != 0; }
     // the tensor's data, or NULL with the error set: no such tensor, or not `numel` elements
     const float* find(const std::string& name, int64_t numel) const {

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "host_params.h"
 #include "philox.h"
+#include "reduce.h"
 #include <math.h>
 #include <string.h>
 #include <string>
@@ -30,8 +31,6 @@ namespace {
 constexpr int NT = 64, NR = 16, PIX = NT * NR;
 constexpr int N_TENSORS = 19;
 constexpr float IN_EPS = 1e-5f, LRELU = 0.2f;
-// the library carries no packed-fp32 arithmetic (Makefile: check-no-packed); the loop vectoriser would form it in the strided loops below
-#define SBC_NO_VEC _Pragma("clang loop vectorize(disable) interleave(disable)")
 
 // stages of one evaluation, in workspace order; floats per image = C * H * W
 enum Stage {
@@ -71,17 +70,7 @@ enum { W_D0A, W_D0B, W_D1A, W_D1B, W_D2A, W_D2B, W_BA, W_BB, W_U0A, W_U0B, W_U1A
 constexpr int64_t tensor_prefix(int t) { return t == 0 ? 0 : tensor_prefix(t - 1) + TENSORS[t - 1].numel; }
 constexpr int64_t NET_FLOATS = tensor_prefix(N_TENSORS);
 
-// ---- reductions over a workgroup, fixed order ---------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
+// ---- reductions over a workgroup, fixed order (the wavefront's: reduce.h) ---------------------------------------------------------
 // 256 threads; red: 4 floats of LDS.  Every thread gets the result.
 template <bool MAX>
 __device__ __forceinline__ float block_reduce256(float v, float* red) {
@@ -546,10 +535,8 @@ int sbc_ldamp_create(const sbc_tensor_ref* tensors, int32_t n_tensors, int32_t n
     SBC_REQUIRE(tensors && out && n_nets >= 1 && n_nets <= 64, "sbc_ldamp_create: need tensors, out and 1 <= n_nets <= 64 (got %d)", n_nets);
     SBC_REQUIRE(n_tensors == n_nets * N_TENSORS, "sbc_ldamp_create: %d nets have %d tensors (got %d)", n_nets, n_nets * N_TENSORS, n_tensors);
     TensorIndex sd;
-    const char* twice = nullptr;
-    const int rc = sd.build("sbc_ldamp_create", tensors, n_tensors, &twice);
+    const int rc = sd.build_unique("sbc_ldamp_create", "tensor", tensors, n_tensors);
     if (rc) return rc;
-    SBC_REQUIRE(!twice, "sbc_ldamp_create: tensor '%s' given twice", twice);
     ParamImage params;
     const size_t base = params.take((size_t)n_nets * NET_FLOATS);
     for (int u = 0; u < n_nets; ++u)

@@ -23,47 +23,16 @@
 // Every stage of the last call stays readable in the caller's workspace (sbc_wgan_stage); no stage shares memory with another.
 #include "common.h"
 #include "host_params.h"
+#include "reduce.h"
 #include "wgan_shared.h"
 #include <math.h>
 #include <string.h>
+#include <map>
 #include <string>
 
 namespace sbc {
 namespace {
-
-typedef float f16v __attribute__((ext_vector_type(16)));
-
-constexpr int NR = 16, NT = 64, NZ = 60, CH = 128, PIX = NR * NT, DENSE = CH * (NR / 4) * (NT / 4);
-constexpr int MAX_EXTRA = 4, MAX_L = 2 + MAX_EXTRA;
-constexpr float BN_EPS = 1e-5f;
-// the library carries no packed-fp32 arithmetic (Makefile: check-no-packed); the loop vectoriser would form it in the strided loops below
-#define SBC_NO_VEC _Pragma("clang loop vectorize(disable) interleave(disable)")
-#define SBC_NO_VEC_NO_UNROLL _Pragma("clang loop vectorize(disable) interleave(disable) unroll(disable)")
-
-// geometry of hidden layer k = 1 .. L (its OUTPUT is H x W; layers 1 and 2 read their input through the nearest x 2 map)
-__host__ __device__ constexpr int layer_h(int k) { return k == 1 ? NR / 2 : NR; }
-__host__ __device__ constexpr int layer_w(int k) { return k == 1 ? NT / 2 : NT; }
-constexpr int layer_ks(int k) { return k <= 2 ? 5 : 3; }
-
-// ---- reductions, fixed order --------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// 256 threads; red: 4 doubles of LDS.  Every thread gets the result.
-__device__ __forceinline__ double block_sum256(double v, double* red) {
-    v = wave_sum(v);
-    __syncthreads();                                   // red may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
+using namespace wgan_shared;                           // the constants, the layers' geometry and the state dict of the generator
 
 // ---- dense: z [60] -> [128][4][16] + bias --------------------------------------------------------------------------------------
 // grid (32, B); feature f = c * 64 + h * 16 + w; the sum runs over j = 0 .. 59 in order
@@ -534,7 +503,7 @@ struct Layout {
         for (int k = L; k >= 1; --k) grad[k] = take((int64_t)CH * layer_h(k) * layer_w(k));
         grad[0] = take(DENSE);
         mask[0] = -1;
-        for (int k = 1; k <= L; ++k) mask[k] = take((int64_t)CH * layer_h(k) * (layer_w(k) / 32));
+        for (int k = 1; k <= L; ++k) mask[k] = take((int64_t)CH * mask_words(layer_h(k), layer_w(k)));
         total = o;
     }
 };
@@ -546,7 +515,6 @@ enum { ST_ACT = 0, ST_GEN = 16, ST_DG = 17, ST_GRAD = 32, ST_MASK = 48 };
 
 // ---- what training launches of this file (wgan_shared.h) --------------------------------------------------------------------------------
 namespace wgan_shared {
-static_assert(NR == sbc::NR && NT == sbc::NT && NZ == sbc::NZ && CH == sbc::CH && MAX_EXTRA == sbc::MAX_EXTRA, "one geometry");
 
 void launch_dense(const float* z, const float* W, const float* bias, float* out, int B, hipStream_t s) {
     hipLaunchKernelGGL(dense_kernel, dim3(DENSE / 256, B), dim3(256), 0, s, z, W, bias, out);
@@ -638,55 +606,51 @@ int sbc_wgan_create(const sbc_tensor_ref* tensors, int32_t n_tensors, sbc_wgan**
     using namespace sbc;
     SBC_REQUIRE(tensors && out && n_tensors > 0, "sbc_wgan_create: need tensors and out");
     TensorIndex sd;
-    const char* twice = nullptr;
-    const int rc = sd.build("sbc_wgan_create", tensors, n_tensors, &twice);
-    if (rc) return rc;
-    SBC_REQUIRE(!twice, "sbc_wgan_create: tensor '%s' given twice", twice);
     int n_extra = 0;
-    while (sd.has("conv.extra_conv" + std::to_string(n_extra) + ".weight")) ++n_extra;
-    SBC_REQUIRE(n_extra <= MAX_EXTRA, "sbc_wgan_create: at most %d extra layers are supported (got %d)", MAX_EXTRA, n_extra);
-    SBC_REQUIRE(n_tensors == 16 + 5 * n_extra, "sbc_wgan_create: a generator with %d extra layers has %d float tensors (got %d)", n_extra,
-                16 + 5 * n_extra, n_tensors);
+    const int rc = open_generator("sbc_wgan_create", tensors, n_tensors, "tensor", sd, &n_extra);
+    if (rc) return rc;
     const int L = 2 + n_extra;
     sbc_wgan* h = new sbc_wgan;
     h->n_extra = n_extra;
     std::vector<float>& host = h->params.host;
     auto take = [&](size_t n) { return h->params.take(n); };
+    std::map<std::string, int64_t> numel;
+    for (const auto& t : generator_tensors(n_extra)) numel.insert(t);
     bool ok = true;                                      // false after the first tensor that is missing or mis-sized: its message stays
-    auto fetch = [&](const std::string& name, int64_t numel) -> const float* {
-        const float* p = ok ? sd.find(name, numel) : nullptr;
+    auto fetch = [&](const std::string& name) -> const float* {
+        const float* p = ok ? sd.find(name, numel.at(name)) : nullptr;
         if (!p) ok = false;
         return p;
     };
-    if (const float* w = fetch("dense.dense_input.weight", (int64_t)DENSE * NZ)) {
-        h->dense_w = take((size_t)DENSE * NZ);
-        memcpy(host.data() + h->dense_w, w, sizeof(float) * DENSE * NZ);
-        h->dense_wt = take((size_t)DENSE * NZ);
-        for (int f = 0; f < DENSE; ++f)
-            for (int j = 0; j < NZ; ++j) host[h->dense_wt + (size_t)j * DENSE + f] = w[(size_t)f * NZ + j];
-    }
-    if (const float* b = fetch("dense.dense_input.bias", DENSE)) {
-        h->dense_b = take(DENSE);
-        memcpy(host.data() + h->dense_b, b, sizeof(float) * DENSE);
-    }
+    // a tensor as it is: at `at`, or behind what is there (returns its offset)
+    auto place = [&](const std::string& name, size_t at) {
+        if (const float* p = fetch(name)) memcpy(host.data() + at, p, sizeof(float) * numel.at(name));
+    };
+    auto add = [&](const std::string& name) {
+        const size_t at = take((size_t)numel.at(name));
+        place(name, at);
+        return at;
+    };
+    h->dense_w = add("dense.dense_input.weight");
+    h->dense_wt = take((size_t)DENSE * NZ);              // and its transpose, for the dense adjoint
+    for (int f = 0; f < DENSE; ++f)
+        for (int j = 0; j < NZ; ++j) host[h->dense_wt + (size_t)j * DENSE + f] = host[h->dense_w + (size_t)f * NZ + j];
+    h->dense_b = add("dense.dense_input.bias");
     for (int k = 1; k <= L && ok; ++k) {
-        const std::string conv = k <= 2 ? "conv.conv" + std::to_string(k) : "conv.extra_conv" + std::to_string(k - 3);
-        const std::string bn = k <= 2 ? "conv.bn" + std::to_string(k) : "conv.extra_bn" + std::to_string(k - 3);
+        const std::string conv = conv_name(k), bn = bn_name(k);
         const int KS = layer_ks(k), CC = KS == 5 ? ConvCfg<5>::CC : ConvCfg<3>::CC;
-        const size_t wn = (size_t)CH * CH * KS * KS;
-        if (const float* w = fetch(conv + ".weight", (int64_t)wn)) {
+        if (const float* w = fetch(conv + ".weight")) {
+            const size_t wn = (size_t)numel.at(conv + ".weight");
             h->fwd[k] = take(wn);
             pack_conv(w, KS, CC, false, host.data() + h->fwd[k]);
             h->adj[k] = take(wn);
             pack_conv(w, KS, CC, true, host.data() + h->adj[k]);
         }
         h->bias[k] = take(CH);
-        if (k <= 2)
-            if (const float* b = fetch(conv + ".bias", CH)) memcpy(host.data() + h->bias[k], b, sizeof(float) * CH);
+        if (k <= 2) place(conv + ".bias", h->bias[k]);
         h->bn[k] = take(4 * CH);
         const char* part[4] = {".running_mean", ".running_var", ".weight", ".bias"};
-        for (int q = 0; q < 4; ++q)
-            if (const float* p = fetch(bn + part[q], CH)) memcpy(host.data() + h->bn[k] + (size_t)q * CH, p, sizeof(float) * CH);
+        for (int q = 0; q < 4; ++q) place(bn + part[q], h->bn[k] + (size_t)q * CH);
         h->scale[k] = take(CH);
         if (ok)
             for (int c = 0; c < CH; ++c) {
@@ -694,14 +658,8 @@ int sbc_wgan_create(const sbc_tensor_ref* tensors, int32_t n_tensors, sbc_wgan**
                 host[h->scale[k] + c] = b4[2 * CH + c] * (1.f / sqrtf(b4[CH + c] + BN_EPS));
             }
     }
-    if (const float* w = fetch("conv.conv_out.weight", 2 * CH * 25)) {
-        h->out_w = take(2 * CH * 25);
-        memcpy(host.data() + h->out_w, w, sizeof(float) * 2 * CH * 25);
-    }
-    if (const float* b = fetch("conv.conv_out.bias", 2)) {
-        h->out_b = take(2);
-        memcpy(host.data() + h->out_b, b, sizeof(float) * 2);
-    }
+    h->out_w = add("conv.conv_out.weight");
+    h->out_b = add("conv.conv_out.bias");
     const int rc_up = ok ? h->params.upload("sbc_wgan_create") : SBC_ERR_INVALID;
     if (rc_up) {
         delete h;
@@ -729,7 +687,7 @@ int sbc_wgan_stage(const sbc_wgan* h, int32_t stage, int32_t B, int64_t* offset,
     const int L = lay.L;
     int64_t off = -1;
     int c = CH, hh = 0, ww = 0;
-    auto dims = [&](int k) { hh = k == 0 ? NR / 4 : layer_h(k); ww = k == 0 ? NT / 4 : layer_w(k); };
+    auto dims = [&](int k) { hh = layer_h(k); ww = layer_w(k); };
     if (stage >= ST_ACT && stage <= ST_ACT + L) { off = lay.act[stage - ST_ACT]; dims(stage - ST_ACT); }
     else if (stage == ST_GEN || stage == ST_DG) { off = stage == ST_GEN ? lay.gen : lay.dg; c = 2; hh = NR; ww = NT; }
     else if (stage >= ST_GRAD && stage <= ST_GRAD + L) { off = lay.grad[stage - ST_GRAD]; dims(stage - ST_GRAD); }

@@ -20,6 +20,7 @@
 // launch sequence run twice gives the same bits.
 #include "common.h"
 #include "host_params.h"
+#include "reduce.h"
 #include "wgan_shared.h"
 #include <math.h>
 #include <string.h>
@@ -28,26 +29,10 @@
 
 namespace sbc {
 namespace {
-using namespace wgan_shared;
+using namespace wgan_shared;                           // the constants, the layers' geometry and the state dict of the generator
 
-typedef float f16v __attribute__((ext_vector_type(16)));
-
-constexpr int NDF = 64, MAX_L = 2 + MAX_EXTRA, MAX_M = MAX_EXTRA + 2;
-constexpr float BN_EPS = 1e-5f, BN_MOMENTUM = 0.1f;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// 256 threads; red: 4 doubles of LDS.  Every thread gets the result.
-__device__ __forceinline__ double block_sum256(double v, double* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
+constexpr int NDF = 64, MAX_M = MAX_EXTRA + 2;          // the critic's width and its last layer's highest index
+constexpr float BN_MOMENTUM = 0.1f;
 
 // ---- batch statistics: per-channel mean and biased variance over B H W, two passes in float64; running statistics ------------------
 // grid (C).  running = (1 - 0.1) running + 0.1 (mean | var N / (N - 1)), as nn.BatchNorm2d in training mode.
@@ -483,28 +468,46 @@ struct Entry {
     int64_t numel;
 };
 
-// the float tensors of one network on the device: trainable ones first (value, gradient, RMSprop square average), then the running statistics
+// the float tensors of one network on the device: trainable ones first (value, gradient, RMSprop square average), then the running
+// statistics.  The values are a ParamImage; the first n_train floats of it have a gradient and a square average at the same offsets.
 struct Net {
+    ParamImage val;
     std::vector<Entry> entries;
-    size_t n_train = 0, n_all = 0;
-    float *val = nullptr, *grad = nullptr, *sq = nullptr;
-    std::vector<float> host;
-    size_t add(const std::string& name, int64_t numel) {
-        const size_t at = n_all;
-        entries.push_back({name, at, numel});
-        n_all += ((size_t)numel + 3) & ~(size_t)3;
-        return at;
-    }
-    const Entry* find(const char* name) const {
+    size_t n_train = 0;
+    float *grad = nullptr, *sq = nullptr;
+    const Entry* find(const std::string& name) const {
         for (const Entry& e : entries)
             if (e.name == name) return &e;
         return nullptr;
     }
+    // reserve every tensor of `names` (trainable ones first, then the running statistics) and copy it from the state dict; false after a miss
+    bool fill(const TensorIndex& sd, const std::vector<std::pair<std::string, int64_t>>& names) {
+        for (const auto& t : names) {
+            const float* p = sd.find(t.first, t.second);
+            if (!p) return false;
+            entries.push_back({t.first, val.take((size_t)t.second), t.second});
+            memcpy(val.host.data() + entries.back().off, p, sizeof(float) * (size_t)t.second);
+            if (t.first.find(".running_") == std::string::npos) n_train = val.host.size();
+        }
+        return true;
+    }
+    // the values to the current device, the gradients and the square averages zeroed beside them
+    int upload(const char* who) {
+        const int rc = val.upload(who);
+        if (rc) return rc;
+        hipError_t e = hipMalloc(&grad, n_train * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc(&sq, n_train * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(grad, 0, n_train * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(sq, 0, n_train * sizeof(float));
+        if (e == hipSuccess) return SBC_OK;
+        set_error("%s: upload of the parameters failed: %s", who, hipGetErrorString(e));
+        return SBC_ERR_HIP;
+    }
     void release() {
-        if (val) (void)hipFree(val);
+        val.release();
         if (grad) (void)hipFree(grad);
         if (sq) (void)hipFree(sq);
-        val = grad = sq = nullptr;
+        grad = sq = nullptr;
     }
 };
 
@@ -521,11 +524,6 @@ int d_layers(int n_extra, DLayer* l) {
     l[M] = {2 * NDF, NR / 4, NT / 4, 1, 1, 1, NR / 4, NT / 4, 1, 0, 0, 0, 0, 0, 0, 0, 0};
     return M;                                            // index of the final layer
 }
-
-constexpr int g_h(int k) { return k == 0 ? NR / 4 : k == 1 ? NR / 2 : NR; }
-constexpr int g_w(int k) { return k == 0 ? NT / 4 : k == 1 ? NT / 2 : NT; }
-constexpr int g_ks(int k) { return k <= 2 ? 5 : 3; }
-int mask_words(int h, int w) { return h * ((w + 31) / 32); }
 
 // stage kinds of sbc_wgan_trainer_stage: id = net base + 16 kind + layer; the generator's base is 0, the critic's 256 (real pass) and 512 (fake)
 enum { K_ACT = 0, K_RAW, K_PRE, K_MASK, K_MEAN, K_VAR, K_GACT, K_DRAW, K_N, ST_GEN = 128, ST_DGEN = 129, ST_ERR = 130 };
@@ -545,14 +543,14 @@ struct Lay {
             for (int q = 0; q < K_N; ++q)
                 for (int j = 0; j <= MAX_M; ++j) d[s][q][j] = -1;
         for (int k = 0; k <= L; ++k) {
-            const int64_t n = (int64_t)CH * g_h(k) * g_w(k) * Bc;
+            const int64_t n = (int64_t)CH * layer_h(k) * layer_w(k) * Bc;
             g[K_ACT][k] = take(n);
             g[K_GACT][k] = take(n);
             if (k == 0) continue;
             g[K_RAW][k] = take(n);
             g[K_PRE][k] = take(n);
             g[K_DRAW][k] = take(n);
-            g[K_MASK][k] = take((int64_t)CH * mask_words(g_h(k), g_w(k)) * Bc);
+            g[K_MASK][k] = take((int64_t)CH * mask_words(layer_h(k), layer_w(k)) * Bc);
             g[K_MEAN][k] = take(CH);
             g[K_VAR][k] = take(CH);
         }
@@ -579,7 +577,7 @@ struct Lay {
         tmp = take(4 * CH);                              // mean(dy), mean(dy xhat); BatchNorm gradients nobody asked for
         int64_t sc = 0;
         for (int k = 1; k <= L; ++k) {
-            const int64_t n = (int64_t)wgrad128_splits((int)Bc, g_h(k), g_w(k), g_ks(k)) * g_ks(k) * g_ks(k) * CH * CH;
+            const int64_t n = (int64_t)wgrad128_splits((int)Bc, layer_h(k), layer_w(k), layer_ks(k)) * layer_ks(k) * layer_ks(k) * CH * CH;
             sc = n > sc ? n : sc;
         }
         scratch = take(sc);
@@ -591,7 +589,7 @@ struct Lay {
 }  // namespace sbc
 
 struct sbc_wgan_trainer {
-    int n_extra = 0, device = 0;
+    int n_extra = 0;
     sbc::Net G, D;
     float* pack = nullptr;               // the generator's filters packed for conv128: per layer forward, adjoint
     size_t fwd[sbc::MAX_L + 1] = {}, adj[sbc::MAX_L + 1] = {};
@@ -644,13 +642,13 @@ struct Ws {
 };
 
 void g_forward(sbc_wgan_trainer* h, const Ws& ws, const float* noise, int B, hipStream_t s) {
-    const float* v = h->G.val;
+    const float* v = h->G.val.dev;
     launch_dense(noise, v + h->dense_w, v + h->dense_b, ws.g(K_ACT, 0), B, s);
     for (int k = 1; k <= ws.lay.L; ++k) {
-        launch_conv128_raw(ws.g(K_ACT, k - 1), h->pack + h->fwd[k], k <= 2 ? v + h->conv_b[k] : nullptr, ws.g(K_RAW, k), g_h(k), g_w(k), g_ks(k),
+        launch_conv128_raw(ws.g(K_ACT, k - 1), h->pack + h->fwd[k], k <= 2 ? v + h->conv_b[k] : nullptr, ws.g(K_RAW, k), layer_h(k), layer_w(k), layer_ks(k),
                            k <= 2 ? 1 : 0, 0, B, s);
-        bn_forward(ws.g(K_RAW, k), ws.g(K_MEAN, k), ws.g(K_VAR, k), h->G.val + h->rm[k], h->G.val + h->rv[k], v + h->bn_w[k], v + h->bn_b[k],
-                   ws.g(K_PRE, k), ws.g(K_ACT, k), ws.gmask(k), B, CH, g_h(k), g_w(k), 1, 0.f, s);
+        bn_forward(ws.g(K_RAW, k), ws.g(K_MEAN, k), ws.g(K_VAR, k), h->G.val.dev + h->rm[k], h->G.val.dev + h->rv[k], v + h->bn_w[k], v + h->bn_b[k],
+                   ws.g(K_PRE, k), ws.g(K_ACT, k), ws.gmask(k), B, CH, layer_h(k), layer_w(k), 1, 0.f, s);
     }
     launch_out_conv(ws.g(K_ACT, ws.lay.L), v + h->out_w, v + h->out_b, ws.base + ws.lay.gen, B, s);
 }
@@ -661,7 +659,7 @@ DconvArgs dconv_args(const DLayer& q, const float* in, const float* w, const flo
 
 // the critic on `input` [B][2][16][64] into the stages of `slot`; err = mean_b D(input), the seed of its backward pass is sign / B
 void d_forward(sbc_wgan_trainer* h, const Ws& ws, int slot, const float* input, int B, float sign, float* loss, hipStream_t s) {
-    float* v = h->D.val;
+    float* v = h->D.val.dev;
     const float* in = input;
     const int M = h->M;
     for (int j = 0; j <= M; ++j) {
@@ -682,7 +680,7 @@ void d_forward(sbc_wgan_trainer* h, const Ws& ws, int slot, const float* input, 
 // backward through the critic from the seed in draw[M]: weight gradients into D.grad (`wgrads`; += with `accumulate`), the gradient
 // with respect to the input into `gin` (or NULL)
 void d_backward(sbc_wgan_trainer* h, const Ws& ws, int slot, const float* input, int B, bool wgrads, int accumulate, float* gin, hipStream_t s) {
-    const float* v = h->D.val;
+    const float* v = h->D.val.dev;
     for (int j = h->M; j >= 0; --j) {
         const DLayer& q = h->dl[j];
         const float* in = j == 0 ? input : ws.d(slot, K_ACT, j - 1);
@@ -704,7 +702,7 @@ void d_backward(sbc_wgan_trainer* h, const Ws& ws, int slot, const float* input,
 
 // backward through the generator from dgen = d loss / d gen: every parameter gradient into G.grad
 void g_backward(sbc_wgan_trainer* h, const Ws& ws, const float* noise, int B, hipStream_t s) {
-    const float* v = h->G.val;
+    const float* v = h->G.val.dev;
     float* gr = h->G.grad;
     const int L = ws.lay.L;
     const float* dgen = ws.base + ws.lay.dgen;
@@ -713,23 +711,23 @@ void g_backward(sbc_wgan_trainer* h, const Ws& ws, const float* noise, int B, hi
     hipLaunchKernelGGL(chan_sum_kernel, dim3(2), dim3(256), 0, s, dgen, gr + h->out_b, B, 2, PIX);
     launch_out_adjoint(dgen, v + h->out_w, ws.g(K_GACT, L), B, s);
     for (int k = L; k >= 1; --k) {
-        const int H = g_h(k), W = g_w(k);
+        const int H = layer_h(k), W = layer_w(k);
         bn_backward(ws.g(K_GACT, k), ws.g(K_RAW, k), ws.gmask(k), ws.g(K_MEAN, k), ws.g(K_VAR, k), v + h->bn_w[k], ws.g(K_DRAW, k), gr + h->bn_w[k],
                     gr + h->bn_b[k], ws.tmp(), B, CH, H, W, 1, 0, 0.f, s);
-        wgrad128(ws.g(K_DRAW, k), ws.g(K_ACT, k - 1), gr + h->conv_w[k], ws.base + ws.lay.scratch, B, H, W, g_ks(k), k <= 2 ? 1 : 0, s);
+        wgrad128(ws.g(K_DRAW, k), ws.g(K_ACT, k - 1), gr + h->conv_w[k], ws.base + ws.lay.scratch, B, H, W, layer_ks(k), k <= 2 ? 1 : 0, s);
         if (k <= 2) hipLaunchKernelGGL(chan_sum_kernel, dim3(CH), dim3(256), 0, s, (const float*)ws.g(K_DRAW, k), gr + h->conv_b[k], B, CH, H * W);
-        launch_conv128_raw(ws.g(K_DRAW, k), h->pack + h->adj[k], nullptr, ws.g(K_GACT, k - 1), H, W, g_ks(k), 0, k <= 2 ? 1 : 0, B, s);
+        launch_conv128_raw(ws.g(K_DRAW, k), h->pack + h->adj[k], nullptr, ws.g(K_GACT, k - 1), H, W, layer_ks(k), 0, k <= 2 ? 1 : 0, B, s);
     }
     hipLaunchKernelGGL(dense_wgrad_kernel, dim3(DENSE * NZ / 256), dim3(256), 0, s, (const float*)ws.g(K_GACT, 0), noise, gr + h->dense_w,
                        gr + h->dense_b, B);
 }
 
 void repack(sbc_wgan_trainer* h, hipStream_t s) {
-    for (int k = 1; k <= 2 + h->n_extra; ++k) launch_repack128(h->G.val + h->conv_w[k], h->pack + h->fwd[k], h->pack + h->adj[k], g_ks(k), s);
+    for (int k = 1; k <= 2 + h->n_extra; ++k) launch_repack128(h->G.val.dev + h->conv_w[k], h->pack + h->fwd[k], h->pack + h->adj[k], layer_ks(k), s);
 }
 
 void rmsprop(const sbc_wgan_trainer* h, const Net& n, float neg_lr, int mode, hipStream_t s) {
-    hipLaunchKernelGGL(rmsprop_kernel, dim3(grid_of(n.n_train)), dim3(256), 0, s, n.val, (const float*)n.grad, n.sq, (long long)n.n_train, neg_lr,
+    hipLaunchKernelGGL(rmsprop_kernel, dim3(grid_of(n.n_train)), dim3(256), 0, s, n.val.dev, (const float*)n.grad, n.sq, (long long)n.n_train, neg_lr,
                        h->alpha, h->one_minus_alpha, h->eps, h->lo, h->hi, mode);
 }
 
@@ -737,43 +735,11 @@ int check_step(const char* who, const sbc_wgan_trainer* h, const float* workspac
     SBC_REQUIRE(h && workspace, "%s: NULL handle or workspace", who);
     SBC_REQUIRE(B_cap >= 1 && B_cap <= 32768, "%s: the workspace capacity must be in [1, 32768] (got %d)", who, B_cap);
     SBC_REQUIRE(B >= 1 && B <= B_cap, "%s: a batch must be in [1, %d], the capacity of the workspace (got %d)", who, B_cap, B);
-    int cur = 0;
-    SBC_CHECK_HIP(hipGetDevice(&cur));
-    SBC_REQUIRE(cur == h->device, "%s: the handle lives on device %d, the current device is %d", who, h->device, cur);
-    return SBC_OK;
+    return h->G.val.check_device(who);
 }
 
-int upload(const char* who, Net& n) {
-    hipError_t e = hipMalloc(&n.val, n.n_all * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&n.grad, n.n_train * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&n.sq, n.n_train * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(n.val, n.host.data(), n.n_all * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(n.grad, 0, n.n_train * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(n.sq, 0, n.n_train * sizeof(float));
-    if (e != hipSuccess) {
-        set_error("%s: upload of the parameters failed: %s", who, hipGetErrorString(e));
-        return SBC_ERR_HIP;
-    }
-    std::vector<float>().swap(n.host);
-    return SBC_OK;
-}
+size_t off_of(const Net& n, const std::string& name) { return n.find(name)->off; }
 
-// reserve every tensor of `names` (trainable ones first: the caller's order) and copy it from the state dict; false after a miss
-bool fill(Net& n, const TensorIndex& sd, const std::vector<std::pair<std::string, int64_t>>& names) {
-    for (const auto& t : names) n.add(t.first, t.second);
-    n.host.assign(n.n_all, 0.f);
-    for (const Entry& e : n.entries) {
-        const float* p = sd.find(e.name, e.numel);
-        if (!p) return false;
-        memcpy(n.host.data() + e.off, p, sizeof(float) * (size_t)e.numel);
-    }
-    return true;
-}
-
-size_t off_of(const Net& n, const std::string& name) { return n.find(name.c_str())->off; }
-
-std::string g_conv(int k) { return k <= 2 ? "conv.conv" + std::to_string(k) : "conv.extra_conv" + std::to_string(k - 3); }
-std::string g_bn(int k) { return k <= 2 ? "conv.bn" + std::to_string(k) : "conv.extra_bn" + std::to_string(k - 3); }
 std::string d_conv(int j, int n_extra) {
     if (j == 0) return "main.initial:2-64:conv";
     if (j <= n_extra) return "main.extra-layers-" + std::to_string(j - 1) + ":64:conv";
@@ -803,17 +769,10 @@ int sbc_wgan_trainer_create(const sbc_wgan_trainer_desc* desc, const sbc_tensor_
     SBC_REQUIRE(desc->lr_d > 0 && desc->lr_g > 0 && desc->alpha >= 0 && desc->alpha < 1 && desc->eps > 0 && desc->clamp_lower <= desc->clamp_upper,
                 "%s: need lr > 0, 0 <= alpha < 1, eps > 0 (a parameter whose gradient and square average are 0 divides 0 by it) and clamp_lower <= clamp_upper", who);
     TensorIndex gsd, dsd;
-    const char* twice = nullptr;
-    int rc = gsd.build(who, gen, n_gen, &twice);
-    if (rc) return rc;
-    SBC_REQUIRE(!twice, "%s: generator tensor '%s' given twice", who, twice);
-    rc = dsd.build(who, disc, n_disc, &twice);
-    if (rc) return rc;
-    SBC_REQUIRE(!twice, "%s: critic tensor '%s' given twice", who, twice);
     int n_extra = 0;
-    while (gsd.has("conv.extra_conv" + std::to_string(n_extra) + ".weight")) ++n_extra;
-    SBC_REQUIRE(n_extra <= MAX_EXTRA, "%s: at most %d extra layers are supported (got %d)", who, MAX_EXTRA, n_extra);
-    SBC_REQUIRE(n_gen == 16 + 5 * n_extra, "%s: a generator with %d extra layers has %d float tensors (got %d)", who, n_extra, 16 + 5 * n_extra, n_gen);
+    int rc = open_generator(who, gen, n_gen, "generator tensor", gsd, &n_extra);
+    if (!rc) rc = dsd.build_unique(who, "critic tensor", disc, n_disc);
+    if (rc) return rc;
     SBC_REQUIRE(n_disc == 7 + 5 * n_extra, "%s: a critic with %d extra layers, as many as the generator has, has %d float tensors (got %d)", who,
                 n_extra, 7 + 5 * n_extra, n_disc);
     const int L = 2 + n_extra;
@@ -821,31 +780,16 @@ int sbc_wgan_trainer_create(const sbc_wgan_trainer_desc* desc, const sbc_tensor_
     h->n_extra = n_extra;
     h->neg_lr_d = (float)-desc->lr_d; h->neg_lr_g = (float)-desc->lr_g; h->alpha = (float)desc->alpha; h->one_minus_alpha = (float)(1.0 - desc->alpha);
     h->eps = (float)desc->eps; h->lo = (float)desc->clamp_lower; h->hi = (float)desc->clamp_upper;
-    // the generator: parameters in the order of its state dict, then the running statistics
-    std::vector<std::pair<std::string, int64_t>> names = {{"dense.dense_input.weight", (int64_t)DENSE * NZ}, {"dense.dense_input.bias", DENSE}};
-    for (int k = 1; k <= L; ++k) {
-        names.push_back({g_conv(k) + ".weight", (int64_t)CH * CH * g_ks(k) * g_ks(k)});
-        if (k <= 2) names.push_back({g_conv(k) + ".bias", CH});
-        names.push_back({g_bn(k) + ".weight", CH});
-        names.push_back({g_bn(k) + ".bias", CH});
-    }
-    names.push_back({"conv.conv_out.weight", 2 * CH * 25});
-    names.push_back({"conv.conv_out.bias", 2});
-    const size_t g_params = names.size();
-    for (int k = 1; k <= L; ++k) {
-        names.push_back({g_bn(k) + ".running_mean", CH});
-        names.push_back({g_bn(k) + ".running_var", CH});
-    }
-    bool ok = fill(h->G, gsd, names);
+    std::vector<std::pair<std::string, int64_t>> names = generator_tensors(n_extra);
+    bool ok = h->G.fill(gsd, names);
     if (ok) {
-        h->G.n_train = h->G.entries[g_params].off;
         h->dense_w = off_of(h->G, "dense.dense_input.weight"); h->dense_b = off_of(h->G, "dense.dense_input.bias");
         h->out_w = off_of(h->G, "conv.conv_out.weight"); h->out_b = off_of(h->G, "conv.conv_out.bias");
         for (int k = 1; k <= L; ++k) {
-            h->conv_w[k] = off_of(h->G, g_conv(k) + ".weight");
-            if (k <= 2) h->conv_b[k] = off_of(h->G, g_conv(k) + ".bias");
-            h->bn_w[k] = off_of(h->G, g_bn(k) + ".weight"); h->bn_b[k] = off_of(h->G, g_bn(k) + ".bias");
-            h->rm[k] = off_of(h->G, g_bn(k) + ".running_mean"); h->rv[k] = off_of(h->G, g_bn(k) + ".running_var");
+            h->conv_w[k] = off_of(h->G, conv_name(k) + ".weight");
+            if (k <= 2) h->conv_b[k] = off_of(h->G, conv_name(k) + ".bias");
+            h->bn_w[k] = off_of(h->G, bn_name(k) + ".weight"); h->bn_b[k] = off_of(h->G, bn_name(k) + ".bias");
+            h->rm[k] = off_of(h->G, bn_name(k) + ".running_mean"); h->rv[k] = off_of(h->G, bn_name(k) + ".running_var");
         }
     }
     // the critic
@@ -859,15 +803,13 @@ int sbc_wgan_trainer_create(const sbc_wgan_trainer_desc* desc, const sbc_tensor_
             names.push_back({d_bn(j, n_extra) + ".bias", q.Co});
         }
     }
-    const size_t d_params = names.size();
     for (int j = 0; j <= h->M; ++j)
         if (h->dl[j].bn) {
             names.push_back({d_bn(j, n_extra) + ".running_mean", h->dl[j].Co});
             names.push_back({d_bn(j, n_extra) + ".running_var", h->dl[j].Co});
         }
-    ok = ok && fill(h->D, dsd, names);
+    ok = ok && h->D.fill(dsd, names);
     if (ok) {
-        h->D.n_train = h->D.entries[d_params].off;
         for (int j = 0; j <= h->M; ++j) {
             DLayer& q = h->dl[j];
             q.w = off_of(h->D, d_conv(j, n_extra) + ".weight");
@@ -877,19 +819,12 @@ int sbc_wgan_trainer_create(const sbc_wgan_trainer_desc* desc, const sbc_tensor_
         }
     }
     rc = ok ? SBC_OK : SBC_ERR_INVALID;
-    if (!rc) {
-        hipError_t e = hipGetDevice(&h->device);
-        if (e != hipSuccess) {
-            set_error("%s: hipGetDevice failed: %s", who, hipGetErrorString(e));
-            rc = SBC_ERR_HIP;
-        }
-    }
-    if (!rc) rc = upload(who, h->G);
-    if (!rc) rc = upload(who, h->D);
+    if (!rc) rc = h->G.upload(who);
+    if (!rc) rc = h->D.upload(who);
     if (!rc) {
         size_t o = 0;
         for (int k = 1; k <= L; ++k) {
-            const size_t n = (size_t)CH * CH * g_ks(k) * g_ks(k);
+            const size_t n = (size_t)CH * CH * layer_ks(k) * layer_ks(k);
             h->fwd[k] = o; o += n;
             h->adj[k] = o; o += n;
         }
@@ -936,8 +871,8 @@ int sbc_wgan_trainer_stage(const sbc_wgan_trainer* h, int32_t stage, int32_t B_c
     else if (stage >= 0 && net <= 2 && kind < K_N && k <= (net == 0 ? lay.L : lay.M)) {
         off = net == 0 ? lay.g[kind][k] : lay.d[net - 1][kind][k];
         c = net == 0 ? CH : lay.dl[k].Co;
-        hh = net == 0 ? g_h(k) : lay.dl[k].Ho;
-        ww = net == 0 ? g_w(k) : lay.dl[k].Wo;
+        hh = net == 0 ? layer_h(k) : lay.dl[k].Ho;
+        ww = net == 0 ? layer_w(k) : lay.dl[k].Wo;
         if (kind == K_MASK) ww = (ww + 31) / 32;
         if (kind == K_MEAN || kind == K_VAR) { hh = ww = 1; per = 0; }
     }
@@ -997,10 +932,9 @@ int sbc_wgan_trainer_copy(sbc_wgan_trainer* h, int32_t net, int32_t what, const 
     SBC_REQUIRE(e, "%s: the %s has no tensor '%s'", who, net == 0 ? "generator" : "critic", name);
     SBC_REQUIRE(e->numel == numel, "%s: tensor '%s' has %lld elements (got %lld)", who, name, (long long)e->numel, (long long)numel);
     SBC_REQUIRE(what == 0 || e->off < n.n_train, "%s: '%s' is a running statistic: it has no gradient and no square average", who, name);
-    int cur = 0;
-    SBC_CHECK_HIP(hipGetDevice(&cur));
-    SBC_REQUIRE(cur == h->device, "%s: the handle lives on device %d, the current device is %d", who, h->device, cur);
-    float* dev = (what == 0 ? n.val : what == 1 ? n.grad : n.sq) + e->off;
+    const int rc = n.val.check_device(who);
+    if (rc) return rc;
+    float* dev = (what == 0 ? n.val.dev : what == 1 ? n.grad : n.sq) + e->off;
     SBC_CHECK_HIP(hipDeviceSynchronize());
     if (!to_device) {
         SBC_CHECK_HIP(hipMemcpy(host, dev, sizeof(float) * (size_t)numel, hipMemcpyDeviceToHost));

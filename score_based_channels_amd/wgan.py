@@ -29,9 +29,9 @@ SEEDED_OUT_GAIN = 2.8
 _ST_ACT, _ST_GEN, _ST_DG, _ST_GRAD, _ST_MASK = 0, 16, 17, 32, 48
 
 
-def _bn_spec(prefix):
-    return [(prefix + '.weight', (NGF,)), (prefix + '.bias', (NGF,)), (prefix + '.running_mean', (NGF,)),
-            (prefix + '.running_var', (NGF,)), (prefix + '.num_batches_tracked', ())]
+def _bn_spec(prefix, c=NGF):
+    return [(prefix + '.weight', (c,)), (prefix + '.bias', (c,)), (prefix + '.running_mean', (c,)), (prefix + '.running_var', (c,)),
+            (prefix + '.num_batches_tracked', ())]
 
 
 def state_dict_spec(n_extra=2):
@@ -56,42 +56,58 @@ def n_extra_of(sd):
     return n
 
 
+def _named_rng(seed, name):
+    """The generator of tensor ``name``: numpy ``PCG64`` keyed by ``(seed, crc32(name))``"""
+    return np.random.Generator(np.random.PCG64([int(seed), zlib.crc32(name.encode())]))
+
+
+def _draw_state_dict(seed, spec, batches, bn, weight):
+    """A state dict of ``spec`` whose tensors are drawn from their own ``_named_rng``: ``num_batches_tracked`` is ``batches``, a BatchNorm
+    tensor ``bn[leaf](rng, shape)``, every other one ``weight(rng, name, leaf, shape)``, as float32."""
+    sd = {}
+    for name, shape in spec:
+        leaf = name.rsplit('.', 1)[1]
+        if leaf == 'num_batches_tracked':
+            sd[name] = np.asarray(batches, np.int64)
+        elif '.bn' in name or '_bn' in name or 'batchnorm' in name:
+            sd[name] = np.asarray(bn[leaf](_named_rng(seed, name), shape), np.float32)
+        else:
+            sd[name] = np.asarray(weight(_named_rng(seed, name), name, leaf, shape), np.float32)
+    return sd
+
+
 def seeded_state_dict(seed, n_extra=2):
     """Deterministic stand-in for trained weights; a tensor's values depend on the seed and its own name only (numpy ``PCG64`` keyed by
     ``(seed, crc32(name))``).  Convolution and dense weights are normal with He scaling, ``sqrt(2 / fan_in)``, where the input went
     through a ReLU and ``sqrt(1 / fan_in)`` where it did not (dense, conv1); their biases are normal of std 0.1.  BatchNorm is
     non-trivial: weight uniform in [0.8, 1.2], bias normal of std 0.1, running mean normal of std 0.2, running variance uniform in
     [0.6, 1.6].  ``conv_out`` is scaled so that the generated channels have about unit variance per entry."""
-    sd = {}
-    for name, shape in state_dict_spec(n_extra):
-        rng = np.random.Generator(np.random.PCG64([int(seed), zlib.crc32(name.encode())]))
-        leaf = name.rsplit('.', 1)[1]
-        if leaf == 'num_batches_tracked':
-            sd[name] = np.asarray(6000, np.int64)
-            continue
-        if '.bn' in name or '_bn' in name:
-            v = {'weight': lambda: rng.uniform(0.8, 1.2, size=shape), 'bias': lambda: 0.1 * rng.standard_normal(shape),
-                 'running_mean': lambda: 0.2 * rng.standard_normal(shape), 'running_var': lambda: rng.uniform(0.6, 1.6, size=shape)}[leaf]()
-        elif leaf == 'bias':
-            v = 0.1 * rng.standard_normal(shape)
-        else:
-            fan_in = float(np.prod(shape[1:]))
-            relu_in = not (name.startswith('dense.') or name.startswith('conv.conv1.'))
-            gain = SEEDED_OUT_GAIN if name.startswith('conv.conv_out.') else np.sqrt(2.0 if relu_in else 1.0)
-            v = gain / np.sqrt(fan_in) * rng.standard_normal(shape)
-        sd[name] = np.asarray(v, np.float32)
-    return sd
+    def weight(rng, name, leaf, shape):
+        if leaf == 'bias':
+            return 0.1 * rng.standard_normal(shape)
+        fan_in = float(np.prod(shape[1:]))
+        relu_in = not (name.startswith('dense.') or name.startswith('conv.conv1.'))
+        gain = SEEDED_OUT_GAIN if name.startswith('conv.conv_out.') else np.sqrt(2.0 if relu_in else 1.0)
+        return gain / np.sqrt(fan_in) * rng.standard_normal(shape)
+
+    bn = {'weight': lambda rng, shape: rng.uniform(0.8, 1.2, size=shape), 'bias': lambda rng, shape: 0.1 * rng.standard_normal(shape),
+          'running_mean': lambda rng, shape: 0.2 * rng.standard_normal(shape), 'running_var': lambda rng, shape: rng.uniform(0.6, 1.6, size=shape)}
+    return _draw_state_dict(seed, state_dict_spec(n_extra), 6000, bn, weight)
+
+
+def _check_geometry(isize, nz, nc, width, width_name, expected, n_extra_layers):
+    isize = [int(v) for v in isize]
+    if isize != [NR, NT] or int(nz) != NZ or int(nc) != NC or int(width) != expected:
+        raise ValueError('only isize = [%d, %d], nz = %d, nc = %d, %s = %d is supported (got isize %s, nz %s, nc %s, %s %s)'
+                         % (NR, NT, NZ, NC, width_name, expected, isize, nz, nc, width_name, width))
+    if not 0 <= int(n_extra_layers) <= MAX_EXTRA:
+        raise ValueError('n_extra_layers must be in [0, %d] (got %r)' % (MAX_EXTRA, n_extra_layers))
+    return int(n_extra_layers)
 
 
 def check_geometry(isize, nz, nc, ngf, n_extra_layers=0):
     """Host-side refusal of what the kernels do not cover."""
-    isize = [int(v) for v in isize]
-    if isize != [NR, NT] or int(nz) != NZ or int(nc) != NC or int(ngf) != NGF:
-        raise ValueError('only isize = [%d, %d], nz = %d, nc = %d, ngf = %d is supported (got isize %s, nz %s, nc %s, ngf %s)'
-                         % (NR, NT, NZ, NC, NGF, isize, nz, nc, ngf))
-    if not 0 <= int(n_extra_layers) <= MAX_EXTRA:
-        raise ValueError('n_extra_layers must be in [0, %d] (got %r)' % (MAX_EXTRA, n_extra_layers))
-    return int(n_extra_layers)
+    return _check_geometry(isize, nz, nc, ngf, 'ngf', NGF, n_extra_layers)
 
 
 def check_state_dict(sd, n_extra):
@@ -149,6 +165,15 @@ def stage_id(name, n_extra):
         if name.startswith(prefix) and name[len(prefix):].isdigit() and lo <= int(name[len(prefix):]) <= L:
             return base + int(name[len(prefix):])
     raise ValueError('no stage %r in a generator with %d extra layers' % (name, n_extra))
+
+
+def _stage_view(ws, off, B, c, h, w, is_mask):
+    """``[B, c, h, w]`` at float offset ``off`` of the workspace tensor ``ws``; a mask's words as int32"""
+    import torch
+    t = ws[off:off + B * c * h * w]
+    if is_mask:
+        t = t.view(torch.int32)
+    return t.view(B, c, h, w)
 
 
 def unpack_mask(words, width):
@@ -218,14 +243,10 @@ class DCGAN_G_Ours(_lib.DeviceHandle):
         """A stage ``[B, C, H, W]`` of the last call, a view of its workspace: ``'dense'`` / ``'act<k>'`` activations, ``'gen'``,
         ``'dG'``, ``'grad<k>'`` = d loss / d (activation k), ``'mask<k>'`` the ReLU sign words of layer k as int32 ``[B, 128, H, W / 32]``
         (``unpack_mask``)."""
-        import torch
         ws, B = self.last_workspace
         off, c, h, w = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32()
         _lib.check(_lib.lib().sbc_wgan_stage(self._h, stage_id(name, self.n_extra), int(B), C.byref(off), C.byref(c), C.byref(h), C.byref(w)))
-        t = ws[off.value:off.value + B * c.value * h.value * w.value]
-        if name.startswith('mask'):
-            t = t.view(torch.int32)
-        return t.view(B, c.value, h.value, w.value)
+        return _stage_view(ws, off.value, B, c.value, h.value, w.value, name.startswith('mask'))
 
 
 class LatentOptimizer:
@@ -297,13 +318,9 @@ class LatentOptimizer:
 NDF = 64
 _KINDS = {'act': 0, 'raw': 1, 'pre': 2, 'mask': 3, 'mean': 4, 'var': 5, 'gact': 6, 'draw': 7}
 _NETS = {'g': 0, 'd0': 1, 'd1': 2}                     # the generator; the critic's pass over real; its pass over fake
+_NET_INDEX = {'g': 0, 'd': 1}                          # sbc_wgan_trainer_copy's net
 RMSPROP_DEFAULTS = dict(lr=5e-5, alpha=0.99, eps=1e-8)
 CLAMP = (-0.01, 0.01)
-
-
-def _disc_bn_spec(prefix, c):
-    return [(prefix + '.weight', (c,)), (prefix + '.bias', (c,)), (prefix + '.running_mean', (c,)), (prefix + '.running_var', (c,)),
-            (prefix + '.num_batches_tracked', ())]
 
 
 def disc_state_dict_spec(n_extra=1):
@@ -314,19 +331,13 @@ def disc_state_dict_spec(n_extra=1):
         raise ValueError('n_extra must be in [0, %d] (got %r)' % (MAX_EXTRA, n_extra))
     t = [('main.initial:%d-%d:conv.weight' % (NC, NDF), (NDF, NC, 4, 4))]
     for i in range(n_extra):
-        t += [('main.extra-layers-%d:%d:conv.weight' % (i, NDF), (NDF, NDF, 3, 3))] + _disc_bn_spec('main.extra-layers-%d:%d:batchnorm' % (i, NDF), NDF)
-    t += [('main.pyramid:%d-%d:conv.weight' % (NDF, 2 * NDF), (2 * NDF, NDF, 4, 4))] + _disc_bn_spec('main.pyramid:%d:batchnorm' % (2 * NDF), 2 * NDF)
+        t += [('main.extra-layers-%d:%d:conv.weight' % (i, NDF), (NDF, NDF, 3, 3))] + _bn_spec('main.extra-layers-%d:%d:batchnorm' % (i, NDF), NDF)
+    t += [('main.pyramid:%d-%d:conv.weight' % (NDF, 2 * NDF), (2 * NDF, NDF, 4, 4))] + _bn_spec('main.pyramid:%d:batchnorm' % (2 * NDF), 2 * NDF)
     return t + [('main.final:%d-1:conv.weight' % (2 * NDF), (1, 2 * NDF, NR // 4, NT // 4))]
 
 
 def check_disc_geometry(isize, nz, nc, ndf, n_extra_layers=0):
-    isize = [int(v) for v in isize]
-    if isize != [NR, NT] or int(nz) != NZ or int(nc) != NC or int(ndf) != NDF:
-        raise ValueError('only isize = [%d, %d], nz = %d, nc = %d, ndf = %d is supported (got isize %s, nz %s, nc %s, ndf %s)'
-                         % (NR, NT, NZ, NC, NDF, isize, nz, nc, ndf))
-    if not 0 <= int(n_extra_layers) <= MAX_EXTRA:
-        raise ValueError('n_extra_layers must be in [0, %d] (got %r)' % (MAX_EXTRA, n_extra_layers))
-    return int(n_extra_layers)
+    return _check_geometry(isize, nz, nc, ndf, 'ndf', NDF, n_extra_layers)
 
 
 def init_state_dicts(seed, n_extra=1):
@@ -334,27 +345,14 @@ def init_state_dicts(seed, n_extra=1):
     N(1, 0.02) and biases 0, running statistics (0, 1, 0 batches); the dense layer and the convolution biases, which ``weights_init`` does
     not touch, keep torch's default U(-1 / sqrt(fan_in), 1 / sqrt(fan_in)).  A tensor's values depend on the seed and its own name only
     (numpy ``PCG64`` keyed by ``(seed, crc32(name))``, like ``seeded_state_dict``)."""
-    out = []
-    for spec in (state_dict_spec(n_extra), disc_state_dict_spec(n_extra)):
-        sd = {}
-        for name, shape in spec:
-            rng = np.random.Generator(np.random.PCG64([int(seed), zlib.crc32(name.encode())]))
-            leaf = name.rsplit('.', 1)[1]
-            is_bn = '.bn' in name or '_bn' in name or 'batchnorm' in name
-            if leaf == 'num_batches_tracked':
-                sd[name] = np.asarray(0, np.int64)
-                continue
-            if is_bn:
-                v = {'weight': lambda: 1.0 + 0.02 * rng.standard_normal(shape), 'bias': lambda: np.zeros(shape),
-                     'running_mean': lambda: np.zeros(shape), 'running_var': lambda: np.ones(shape)}[leaf]()
-            elif name.startswith('dense.') or leaf == 'bias':
-                fan_in = NZ if name.startswith('dense.') else NGF * 25
-                v = rng.uniform(-1.0, 1.0, size=shape) / np.sqrt(fan_in)
-            else:
-                v = 0.02 * rng.standard_normal(shape)
-            sd[name] = np.asarray(v, np.float32)
-        out.append(sd)
-    return tuple(out)
+    def weight(rng, name, leaf, shape):
+        if name.startswith('dense.') or leaf == 'bias':
+            return rng.uniform(-1.0, 1.0, size=shape) / np.sqrt(NZ if name.startswith('dense.') else NGF * 25)
+        return 0.02 * rng.standard_normal(shape)
+
+    bn = {'weight': lambda rng, shape: 1.0 + 0.02 * rng.standard_normal(shape), 'bias': lambda rng, shape: np.zeros(shape),
+          'running_mean': lambda rng, shape: np.zeros(shape), 'running_var': lambda rng, shape: np.ones(shape)}
+    return tuple(_draw_state_dict(seed, spec, 0, bn, weight) for spec in (state_dict_spec(n_extra), disc_state_dict_spec(n_extra)))
 
 
 class DCGAN_D:
@@ -450,79 +448,69 @@ class Trainer(_lib.DeviceHandle):
         with torch.cuda.device(dev), torch.cuda.stream(s):
             return x.detach().to(dev, torch.float32).contiguous()
 
-    def critic_step(self, real, noise, stream=None):
+    def _step(self, launch, inputs, n_out, stream):
+        """One iteration: ``launch(handle, (pointer, batch) of every input, out, workspace, capacity, stream)`` on ``inputs``
+        ``[(array, shape of a sample, name)]`` -> (its float32 ``[n_out]`` losses on the device, the batch of every input)"""
         import torch
         dev, s, ws = self._prepare(stream)
-        real, noise = self._input(real, (NC, NR, NT), 'real', dev, s), self._input(noise, (NZ,), 'noise', dev, s)
+        xs = [self._input(x, shape, name, dev, s) for x, shape, name in inputs]
         with torch.cuda.device(dev):
             with torch.cuda.stream(s):
-                out = torch.empty(2, dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib().sbc_wgan_trainer_critic_step(self._h, C.c_void_p(real.data_ptr()), real.shape[0], C.c_void_p(noise.data_ptr()),
-                                                               noise.shape[0], C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), self.capacity,
-                                                               C.c_void_p(s.cuda_stream)))
-            for t in (real, noise, ws, out):
+                out = torch.empty(n_out, dtype=torch.float32, device=dev)
+            args = [a for x in xs for a in (C.c_void_p(x.data_ptr()), x.shape[0])]
+            _lib.check(launch(self._h, *args, C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), self.capacity, C.c_void_p(s.cuda_stream)))
+            for t in xs + [ws, out]:
                 t.record_stream(s)
             out.record_stream(torch.cuda.current_stream(dev))
+        return out, [x.shape[0] for x in xs]
+
+    def critic_step(self, real, noise, stream=None):
+        out, (b_real, b_fake) = self._step(_lib.lib().sbc_wgan_trainer_critic_step, [(real, (NC, NR, NT), 'real'), (noise, (NZ,), 'noise')], 2, stream)
         self._tracked[0] += 1
         self._tracked[1] += 2
         self.steps[1] += 1
-        self.last_batch = {'g': noise.shape[0], 'd0': real.shape[0], 'd1': noise.shape[0]}
+        self.last_batch = {'g': b_fake, 'd0': b_real, 'd1': b_fake}
         return out
 
     def generator_step(self, noise, stream=None):
-        import torch
-        dev, s, ws = self._prepare(stream)
-        noise = self._input(noise, (NZ,), 'noise', dev, s)
-        with torch.cuda.device(dev):
-            with torch.cuda.stream(s):
-                out = torch.empty(1, dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib().sbc_wgan_trainer_generator_step(self._h, C.c_void_p(noise.data_ptr()), noise.shape[0], C.c_void_p(out.data_ptr()),
-                                                                  C.c_void_p(ws.data_ptr()), self.capacity, C.c_void_p(s.cuda_stream)))
-            for t in (noise, ws, out):
-                t.record_stream(s)
-            out.record_stream(torch.cuda.current_stream(dev))
+        out, (b,) = self._step(_lib.lib().sbc_wgan_trainer_generator_step, [(noise, (NZ,), 'noise')], 1, stream)
         self._tracked[0] += 1
         self._tracked[1] += 1
         self.steps[0] += 1
-        self.last_batch.update({'g': noise.shape[0], 'd1': noise.shape[0]})
+        self.last_batch.update({'g': b, 'd1': b})
         return out
 
     def stage(self, name):
         """A stage of the last call as a view of the workspace: ``[B, C, H, W]`` of the batch that wrote it, ``[C]`` for ``mean`` / ``var`` /
         ``err``; masks as int32 words (``unpack_mask``)."""
-        import torch
         off, c, h, w, per = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         _lib.check(_lib.lib().sbc_wgan_trainer_stage(self._h, trainer_stage_id(name, self.n_extra), self.capacity, C.byref(off), C.byref(c),
                                                      C.byref(h), C.byref(w), C.byref(per)))
         if not per.value:
             return self._ws[off.value:off.value + c.value]
-        B = self.last_batch[name.partition('.')[0]]
-        t = self._ws[off.value:off.value + B * c.value * h.value * w.value]
-        if '.mask' in name:
-            t = t.view(torch.int32)
-        return t.view(B, c.value, h.value, w.value)
+        return _stage_view(self._ws, off.value, self.last_batch[name.partition('.')[0]], c.value, h.value, w.value, '.mask' in name)
 
     def _copy(self, net, name, what, arr, to_device):
         import torch
-        net_i, what_i = {'g': 0, 'd': 1}[net], {'value': 0, 'grad': 1, 'square_avg': 2}[what]
+        net_i, what_i = _NET_INDEX[net], {'value': 0, 'grad': 1, 'square_avg': 2}[what]
         with torch.cuda.device(self._torch_device()):
             _lib.check(_lib.lib().sbc_wgan_trainer_copy(self._h, net_i, what_i, name.encode(), arr.ctypes.data_as(C.c_void_p), arr.size, int(to_device)))
 
     def tensor(self, net, name, what='value'):
         """Tensor ``name`` of net ``'g'`` / ``'d'`` as a numpy array: its ``'value'``, ``'grad'`` or ``'square_avg'``.  Waits for the device."""
-        arr = np.empty(self._shapes[{'g': 0, 'd': 1}[net]][name], np.float32)
+        arr = np.empty(self._shapes[_NET_INDEX[net]][name], np.float32)
         self._copy(net, name, what, arr, False)
         return arr
 
     def set_tensor(self, net, name, value, what='value'):
         arr = np.ascontiguousarray(value, np.float32)
-        if arr.shape != tuple(self._shapes[{'g': 0, 'd': 1}[net]][name]):
-            raise ValueError('size mismatch for %s: %s vs %s' % (name, arr.shape, self._shapes[{'g': 0, 'd': 1}[net]][name]))
+        if arr.shape != tuple(self._shapes[_NET_INDEX[net]][name]):
+            raise ValueError('size mismatch for %s: %s vs %s' % (name, arr.shape, self._shapes[_NET_INDEX[net]][name]))
         self._copy(net, name, what, arr, True)
 
     def parameter_names(self, net):
         """The trainable tensors in ``parameters()`` order"""
-        return [n for n in self._names[{'g': 0, 'd': 1}[net]] if not n.endswith(('running_mean', 'running_var'))]
+        return [n for n in self._names[_NET_INDEX[net]] if not n.endswith(('running_mean', 'running_var'))]
 
     def state_dicts(self):
         out = []
