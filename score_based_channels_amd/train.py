@@ -142,6 +142,7 @@ class TrainNet:
         self.scratch = torch.zeros(scr, **f32)                        # weight-gradient partials (side stream, in order)
         self.scratch_main = torch.zeros(int(lib.sbc_wgrad_scratch_floats(B, self.nt, self.nr, self.ngf, self.channels, 3)), **f32)
         self.gbuf, self.pool_grad = {}, {}
+        self._records = {}
 
     # --- checkpoint grammar -----------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, strict=True):
@@ -436,7 +437,12 @@ class TrainNet:
             for i, o in enumerate(ops):
                 o.tag = (100 if i < n_fwd else 200) + o.kind
             plans[replay] = _lib.Plan(ops, keepalive=keep)
+            self._records[mode, replay] = tuple(ops)
         return plans
+
+    def records(self, mode, replay=False):
+        """The ``sbc_op`` records the plan of ``mode`` (``_build``) was made from, once that plan exists: read-only, for inspection."""
+        return self._records[mode, bool(replay)]
 
     def _run(self, mode, samples, labels, noise, use_graph=False):
         if mode not in self._plans:

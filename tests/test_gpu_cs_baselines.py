@@ -7,6 +7,7 @@ import torch
 import cs_checks as K
 import cs_oracle as O
 from conftest import rel_err, rel_err_elementwise
+from guarded import cplx as _cplx, planes as _planes, ptr as _ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -385,3 +386,65 @@ def test_ml_cli_at_alpha_0p2(tmp_path, monkeypatch):
     assert ref['oracle_log'].min() >= 0.5
     assert err <= 1e-5, err
 
+
+
+# ---- outputs and logs between guarded margins (tests/guarded.py): one geometry per dispatch path --------------------------------------
+@pytest.mark.parametrize('L', [1, 2, 4])
+def test_l1_with_guarded_operands(L):
+    """l1_lifted_kernel<1>, <2>, <4> through sbc_l1_lifted_run directly: the problem and the bounds of test_l1_first_steps_match_the_oracle
+    (three steps), no write outside H_hat, X and the log, no input touched, and the bits the Python wrapper returns."""
+    import ctypes as C
+    from guarded import Guard
+    from score_based_channels_amd import _lib
+    P, Y, H = _data(3, 38, 11, 10.0)
+    B, steps, lam, lr = 3, 3, 0.3, 3e-3
+    g = Guard(torch)
+    d = {k: g.inp(k, a) for k, a in dict(P=_planes(P), Y=_planes(Y), Htrue=_planes(H), p_index=np.arange(B, dtype=np.int32),
+                                         h_index=np.arange(B, dtype=np.int32), lmbda=np.full(B, lam, np.float32), lr=np.full(B, lr, np.float32)).items()}
+    log, Hh, X = g.out('nmse log', (steps, B)), g.out('H_hat', (B, 64, 16, 2)), g.out('X', (B, 64 * L, 16 * L, 2))
+    desc = _lib.sbc_l1_lifted_desc(nmse=_ptr(log), H_hat=_ptr(Hh), X=_ptr(X), B=B, nP=B, nH=B, Nt=64, Nr=16, Np=38, lifting=L, steps=steps,
+                                   **{k: _ptr(t) for k, t in d.items()})
+    _lib.check(_lib.lib().sbc_l1_lifted_run(C.byref(desc), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()
+    g.check()
+    log, Hh, X = log.cpu().numpy(), _cplx(Hh), _cplx(X)
+    rlog, rH, rX = O.l1_run(P, Y, H, lam, lr, L, steps)
+    assert rel_err_elementwise(_ri(X), _ri(rX)) < 1e-5 and rel_err_elementwise(_ri(Hh), _ri(rH)) < 1e-5
+    assert np.max(np.abs(log / rlog - 1)) < 5e-6
+    wlog, wH, wX = _gpu_l1(P, Y, H, lam, lr, L, steps, want_x=True)
+    assert log.tobytes() == wlog.tobytes() and Hh.tobytes() == wH.tobytes() and X.tobytes() == wX.tobytes()
+
+
+@pytest.mark.parametrize('with_h', [True, False])
+def test_ls_with_guarded_operands(with_h):
+    """sbc_ls_regularized directly, with and without Htrue: a problem and the bounds of test_ls_geometry_grid, no write outside H_hat
+    and nmse, no input touched, and the bits the Python wrapper returns."""
+    import ctypes as C
+    from guarded import Guard
+    from score_based_channels_amd import _lib
+    npil, nt, nr = 38, 64, 16
+    P, Y, H, pidx, hidx, noise = K.ls_problem(npil, nt, nr, 1000 + 7 * npil + nt + nr)
+    B = Y.shape[0]
+    g = Guard(torch)
+    d = {k: g.inp(k, a) for k, a in dict(P=_planes(P), Y=_planes(Y), p_index=np.asarray(pidx, np.int32), noise_var=np.asarray(noise, np.float32)).items()}
+    if with_h:
+        d.update(Htrue=g.inp('Htrue', _planes(H)), h_index=g.inp('h_index', np.asarray(hidx, np.int32)))
+    Hh, nmse = g.out('H_hat', (B, nt, nr, 2)), g.out('nmse', (B,)) if with_h else None
+    desc = _lib.sbc_ls_desc(H_hat=_ptr(Hh), nmse=_ptr(nmse), B=B, nP=P.shape[0], nH=H.shape[0] if with_h else 0, Nt=nt, Nr=nr, Np=npil,
+                            **{k: _ptr(t) for k, t in d.items()})
+    _lib.check(_lib.lib().sbc_ls_regularized(C.byref(desc), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()
+    g.check()
+    wH, wn = _gpu_ls(P, Y, noise, H if with_h else None, p_index=pidx, **(dict(h_index=hidx) if with_h else {}))
+    Hh = _cplx(Hh)
+    assert Hh.tobytes() == wH.tobytes()
+    if with_h:
+        nmse = nmse.cpu().numpy()
+        assert nmse.tobytes() == wn.tobytes()
+        figures, failures = K.check_ls(Hh, nmse, P[pidx], Y, H[hidx], noise)
+        assert len(figures) == 4 and not failures, failures
+    else:
+        assert wn is None
+        figures, failures = K.check_ls(Hh, None, P[pidx], Y, None, noise)          # the bounds of test_ls_geometry_grid on the estimate
+        assert len(figures) == 4 and not failures, failures
+        assert Hh.tobytes() == _gpu_ls(P, Y, noise, H, p_index=pidx, h_index=hidx)[0].tobytes()      # and the bits of the Htrue case

@@ -16,6 +16,7 @@ import torch
 import ldamp_cases as LC
 import ldamp_oracle as O
 from conftest import load_golden
+from guarded import cplx as _cplx, planes as _planes
 from score_based_channels_amd import _lib, ldamp
 
 pytestmark = pytest.mark.gpu
@@ -358,3 +359,104 @@ def test_rejected_settings_raise(model, weights):
         assert field in _lib.lib().sbc_last_error().decode()
     torch.cuda.synchronize()
     assert torch.all(out == 7.0)
+
+
+# ---- guarded operands, and a workspace of exactly sbc_ldamp_workspace_floats(B, num_unrolls) floats (tests/guarded.py) -----------------
+# Through the C calls directly, as test_rejected_settings_raise does: every operand, output and log is a view into a larger allocation
+# with guarded margins, the workspace has exactly the documented size between pads of one per-sample stride and starts as NaN (the
+# library promises nothing about what it holds), and the results are held to the rule with the references the tests above share.
+
+def _guarded_workspace(g, B, U):
+    f = _lib.lib().sbc_ldamp_workspace_floats
+    n = int(f(B, U))
+    assert n > 0
+    return g.out('workspace (%d floats, B %d unrolls %d)' % (n, B, U), (n,), must_write=False, pad=max(1024, int(f(B + 1, U)) - n))
+
+
+def guarded_denoise(m, net, r):
+    from guarded import Guard
+    g = Guard(torch, 'cuda:0')
+    B = r.shape[0]
+    p = lambda t: C.c_void_p(t.data_ptr())                           # noqa: E731
+    dr, out, ws = g.inp('r', _planes(r)), g.out('out', (B, 64, 16, 2)), _guarded_workspace(g, B, 0)
+    _lib.check(_lib.lib().sbc_ldamp_denoise(m._h, int(net), p(dr), p(out), B, p(ws), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()
+    g.check()
+    return _cplx(out)
+
+
+def guarded_run(m, Y, P, eig, d, U, H=None):
+    from guarded import Guard
+    g = Guard(torch, 'cuda:0')
+    B, Np = Y.shape[:2]
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
+    inp = {k: g.inp(k, a) for k, a in dict(Y_herm=_planes(Y), P_herm=_planes(P), eig1=np.asarray(eig, np.float32), directions=d[:U]).items()}
+    dH = g.inp('Htrue', _planes(H)) if H is not None else None
+    out = dict(H_hat=g.out('H_hat', (B, 64, 16, 2)), h_log=g.out('h_log', (U, B, 64, 16, 2)), z_log=g.out('z_log', (U, B, Np, 16, 2)),
+               div_log=g.out('div_log', (U, B)), eps_log=g.out('eps_log', (U, B)))
+    nmse = g.out('nmse', (B,)) if H is not None else None
+    ws = _guarded_workspace(g, B, U)
+    desc = _lib.sbc_ldamp_run_desc(Htrue=p(dH), nmse=p(nmse), workspace=p(ws), B=B, Np=Np, Nt=64, Nr=16, num_unrolls=U,
+                                   **{k: p(t) for k, t in list(inp.items()) + list(out.items())})
+    _lib.check(_lib.lib().sbc_ldamp_run(m._h, C.byref(desc), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()
+    g.check()
+    L = {'H_hat': _cplx(out['H_hat']), 'h': _cplx(out['h_log']), 'z': _cplx(out['z_log']), 'div': out['div_log'].cpu().numpy(),
+         'eps': out['eps_log'].cpu().numpy()}
+    if nmse is not None:
+        L['nmse'] = nmse.cpu().numpy()
+    return L
+
+
+@pytest.mark.parametrize('B', [1, 3])
+def test_denoise_with_guarded_operands_and_an_exact_workspace(model, B):
+    """unrolls = 0: one evaluation.  The first B samples of the reference fixture, held to the fixture's bound; and the Python host's call
+    (its workspace is the allocator's) returns the same bits."""
+    g = O.golden_unet()
+    got = guarded_denoise(model, 0, g['r'][:B])
+    err, e_ref = O.normwise(got, g['out64'][:B]), O.normwise(g['out32'], g['out64'])
+    print('guarded denoise B %d: kernel %.3e   e_ref %.3e' % (B, err, e_ref))
+    assert err <= FACTOR * e_ref
+    assert np.array_equal(got, model.denoise(0, dev(g['r'][:B])).cpu().numpy())
+
+
+@pytest.mark.parametrize('U', [1, 3])
+@pytest.mark.parametrize('B', [1, 3])
+def test_the_loop_with_guarded_operands_and_an_exact_workspace(B, U):
+    """The first B samples and the first U unrolls of the plain loop case: h, z, div, eps per unroll within the bound test_the_loop_under_regimes
+    holds the whole case to (e_ref of its four samples), the NMSE of the library's own estimate, and the same bits as the Python host's call."""
+    case = LC.MIXED[0]
+    m = model_of(case.weights, LC.UNROLLS)
+    Y, P, eig, d = LC.loop_problem(case)
+    H = O.synthetic_problem(Y.shape[0], Y.shape[1], case.snr_db, LC.LOOP_SEED)[3]
+    L = guarded_run(m, Y[:B], P[:B], eig[:B], d[:, :B], U, H[:B])
+    r64, r32, r32f = LC.loop_refs(case)
+    bad = []
+    for k in range(U):
+        for q, kind in (('h', 'norm'), ('z', 'norm'), ('div', 'abs'), ('eps', 'abs')):
+            err = LC.errors(L[q][k], r64[q][k][:B], kind)
+            e_ref = max(float(np.max(LC.errors(r32[q][k], r64[q][k], kind))), float(np.max(LC.errors(r32f[q][k], r64[q][k], kind))))
+            slack = LC.ULP * np.abs(np.asarray(r64[q][k][:B], np.float64)).reshape(-1) if kind == 'abs' else 0.0
+            print('guarded B %d U %d unroll %d %-3s error %.3e   e_ref %.3e' % (B, U, k, q, float(np.max(err)), e_ref))
+            if not (np.all(np.isfinite(err)) and e_ref > 0 and np.all(err <= FACTOR * e_ref + slack)):
+                bad.append((k, q, float(np.max(err)), e_ref))
+    assert not bad, bad
+    assert np.array_equal(L['H_hat'], L['h'][U - 1])
+    nm = np.sum(np.abs(L['H_hat'] - H[:B]) ** 2, (1, 2)) / np.sum(np.abs(H[:B]) ** 2, (1, 2))
+    assert np.max(np.abs(L['nmse'] / nm - 1)) < 1e-5
+    want = run_logs(m, Y[:B], P[:B], eig[:B], d[:U, :B], unrolls=U)
+    for k in ('h', 'z', 'div', 'eps', 'H_hat'):
+        assert np.array_equal(L[k], want[k]), k
+
+
+def test_a_mixed_batch_with_guarded_operands_and_an_exact_workspace():
+    """The batch of test_a_mixed_batch_equals_its_single_sample_calls: guarded, it returns the bits the Python host's call returns.  The link
+    to a reference is indirect here: that test ties the host call's bits to the single-sample calls, and test_the_loop_under_regimes holds
+    those to the oracle; the guarded B / unroll grid above compares with the references itself."""
+    m = model_of('plain', LC.UNROLLS)
+    Y, P, eig, d = LC.mixed_problem()
+    L = guarded_run(m, Y, P, eig, d, LC.UNROLLS)
+    want = run_logs(m, Y, P, eig, d)
+    assert L['eps'][0, 1] == np.float32(LC.EPS_FLOOR) and np.all(np.isfinite(L['h']))
+    for k in ('h', 'z', 'div', 'eps', 'H_hat'):
+        assert np.array_equal(L[k], want[k]), k

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 
 from conftest import rel_err, rel_err_elementwise
+import guarded
+from guarded import current as _G, dev as _dev, out as _out, pointer_fields
 from oracle import ncsnv2_oracle as O
 from plan_interp import inorm_stats
 
@@ -24,14 +26,20 @@ def gpu():
     return torch, _lib
 
 
-def _dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+# Every tensor a launch reads or writes is a view into a larger allocation with guarded margins (tests/guarded.py): `_dev` uploads an
+# operand between +inf pads, `_out` hands out a NaN-filled output of exactly the stated size between sentinel pads, and `_launch`
+# checks after its synchronise that no pad and no input changed and that the outputs were written.  One Guard per test.
+@pytest.fixture(autouse=True)
+def _guard(gpu):
+    yield guarded.begin(gpu[0])
+    guarded.end()
 
 
 def _launch(gpu, op):
     torch, _lib = gpu
     _lib.check(_lib.lib().sbc_op_launch(C.byref(op), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
+    _G.check(touched=pointer_fields(op))
 
 
 def _p(t):
@@ -248,9 +256,9 @@ def test_conv_matches_oracle(gpu, cin, cout, k, dil, B, H, W, mode, algo):
         up = rng.standard_normal((B, uh, uw, cout)).astype(F32)
         ref = ref + O.bilinear_align_corners(up.transpose(0, 3, 1, 2), (H, W)).transpose(0, 2, 3, 1)
 
-    d = {k_: _dev(torch, a) for k_, a in dict(x=x, w=pack_conv_weight(w), bias=bias, stats=stats, res1=res1,
+    d = {k_: _dev(torch, a, k_) for k_, a in dict(x=x, w=pack_conv_weight(w), bias=bias, stats=stats, res1=res1,
                                               res2=res2, up=up).items() if a is not None}
-    out = torch.full((B, Ho, Wo, cout), float('nan'), dtype=torch.float32, device='cuda')
+    out = _out((B, Ho, Wo, cout), 'out')
     op = _lib.sbc_op(kind=P.CONV, flags=flags, B=B, H=H, W=W, cin=cin, cout=cout, ksize=k, dil=dil,
                      in_=_p(d['x']), out=_p(out), weight=_p(d['w']))
     for name in ('bias', 'stats', 'res1', 'res2', 'up'):
@@ -317,7 +325,7 @@ def test_conv_two_wave_groups_are_race_free(gpu, cin, cout, B):
     w = (rng.standard_normal((cout, cin, 3, 3)) / np.sqrt(cin * 9)).astype(F32)
     ref = O.conv2d(x.transpose(0, 3, 1, 2), w, None, 1).transpose(0, 2, 3, 1)
     dx, dw = _dev(torch, x), _dev(torch, pack_conv_weight_winograd_split(w).view(np.float32))
-    outs = [torch.full((B, H, W, cout), float('nan'), dtype=torch.float32, device='cuda') for _ in range(2)]
+    outs = [_out((B, H, W, cout)) for _ in range(2)]
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     first = None
     for rep in range(300):
@@ -343,12 +351,14 @@ def test_conv_two_wave_groups_are_race_free(gpu, cin, cout, B):
         sums.append((out.view(torch.int32).to(torch.int64)).sum())
     sums = torch.stack(sums).cpu().numpy()
     assert (sums == sums[0]).all()
+    torch.cuda.synchronize()
+    _G.check()
 
 
 def test_conv_rejects_unsupported_shapes(gpu):
     torch, _lib = gpu
     from score_based_channels_amd import plan as P
-    t = torch.zeros(16, device='cuda')
+    t = _out((16,), fill=0.0)                       # (never read or written: every launch below is refused)
     op = _lib.sbc_op(kind=P.CONV, B=1, H=8, W=8, cin=48, cout=32, ksize=3, dil=1, in_=_p(t), out=_p(t), weight=_p(t))
     rc = _lib.lib().sbc_op_launch(C.byref(op), None)
     assert rc == -3 and b'no kernel' in _lib.lib().sbc_last_error()
@@ -370,7 +380,7 @@ def test_inorm_stats_matches_oracle(gpu, C_, B, H, W):
     agb = np.stack(((1 + 0.1 * rng.standard_normal(C_)), (1 + 0.1 * rng.standard_normal(C_)),
                     0.1 * rng.standard_normal(C_))).astype(F32)
     dx, dagb = _dev(torch, x), _dev(torch, agb)
-    out = torch.zeros(B, 3, C_, device='cuda')
+    out = _out((B, 3, C_), 'out')
     _launch(gpu, _lib.sbc_op(kind=P.INORM_STATS, B=B, H=H, W=W, cin=C_, cout=C_, in_=_p(dx), out=_p(out), weight=_p(dagb)))
     ref = inorm_stats(x, agb[0], agb[1], agb[2])
     got = out.cpu().numpy()
@@ -389,7 +399,7 @@ def test_maxpool5_matches_oracle(gpu, C_, B, H, W, elu):
     from score_based_channels_amd import plan as P
     x = np.random.default_rng(3).standard_normal((B, H, W, C_)).astype(F32)
     dx = _dev(torch, x)
-    out = torch.zeros_like(dx)
+    out = _out(x.shape, 'out')
     _launch(gpu, _lib.sbc_op(kind=P.MAXPOOL5, flags=P.PRO_ELU if elu else 0, B=B, H=H, W=W, cin=C_, cout=C_,
                              in_=_p(dx), out=_p(out)))
     ref = O.max_pool5(x.transpose(0, 3, 1, 2)).transpose(0, 2, 3, 1)
@@ -406,11 +416,22 @@ def test_begin_conv_matches_oracle(gpu, B, H, W):
     w = (rng.standard_normal((32, 2, 3, 3)) / 4).astype(F32)
     b = rng.standard_normal(32).astype(F32)
     dx, dw, db = _dev(torch, x), _dev(torch, w), _dev(torch, b)
-    out = torch.zeros(B, H, W, 32, device='cuda')
+    out = _out((B, H, W, 32), 'out')
     _launch(gpu, _lib.sbc_op(kind=P.BEGIN_CONV, B=B, H=H, W=W, cin=2, cout=32, ksize=3, dil=1, in_=_p(dx), out=_p(out),
                              weight=_p(dw), bias=_p(db)))
     ref = O.conv2d((2 * x - 1).transpose(0, 3, 1, 2), w, b).transpose(0, 2, 3, 1)
     assert rel_err(out.cpu().numpy(), ref) < 1e-5
+    if 128 % W == 0 and H % (128 // W) == 0:
+        # SBC_EPI_MOMENTS_OUT (workgroups of one 128-pixel tile): the same output, and its tile moments in an `aux` of exactly [B][H*W/128][cout][2] floats
+        nt = H * W // 128
+        out2, pm = _out((B, H, W, 32), 'out (with moments)'), _out((B, nt, 32, 2), 'aux (tile moments)')
+        _launch(gpu, _lib.sbc_op(kind=P.BEGIN_CONV, flags=P.EPI_MOMENTS_OUT, B=B, H=H, W=W, cin=2, cout=32, ksize=3, dil=1, in_=_p(dx),
+                                 out=_p(out2), weight=_p(dw), bias=_p(db), aux=_p(pm)))
+        assert rel_err(out2.cpu().numpy(), ref) < 1e-5
+        tiles = out2.cpu().numpy().astype(np.float64).reshape(B, nt, 128, 32)
+        gm = pm.cpu().numpy()
+        assert np.abs(gm[..., 0] - tiles.mean(2)).max() < 1e-5 * max(1.0, np.abs(tiles.mean(2)).max())
+        assert rel_err(gm[..., 1], ((tiles - tiles.mean(2, keepdims=True)) ** 2).sum(2)) < 1e-5
 
 
 @pytest.mark.parametrize('B,H,W', [(5, 64, 16), (1, 256, 64), (40, 8, 8)])
@@ -427,7 +448,7 @@ def test_end_conv_matches_oracle(gpu, B, H, W):
     sigmas = np.exp(np.linspace(np.log(39.15), np.log(3.6e-4), 50)).astype(F32)
     labels = rng.integers(0, 50, B)
     d = [_dev(torch, a) for a in (x, stats, w, b, sigmas, labels.astype(np.int64))]
-    out = torch.zeros(B, H, W, 2, device='cuda')
+    out = _out((B, H, W, 2), 'out')
     ext = _lib.sbc_endconv(sigmas=_p(d[4]), labels=_p(d[5]))
     _launch(gpu, _lib.sbc_op(kind=P.END_CONV, B=B, H=H, W=W, cin=32, cout=2, ksize=3, dil=1, in_=_p(d[0]), out=_p(out),
                              weight=_p(d[2]), bias=_p(d[3]), stats=_p(d[1]), ext=C.cast(C.pointer(ext), C.c_void_p)))
@@ -455,7 +476,7 @@ def test_end_conv_with_its_own_statistics_matches_oracle(gpu, B, H, W):
     d = [_dev(torch, a) for a in (x, agb, w, b, sigmas, labels.astype(np.int64))]
 
     def run(lo, hi):
-        out = torch.full((hi - lo, H, W, 2), float('nan'), device='cuda')
+        out = _out((hi - lo, H, W, 2))
         ext = _lib.sbc_endconv(sigmas=_p(d[4]), labels=_p(d[5][lo:hi]))
         _launch(gpu, _lib.sbc_op(kind=P.END_CONV, flags=P.PRO_NORM_SELF, B=hi - lo, H=H, W=W, cin=32, cout=2, ksize=3, dil=1, in_=_p(d[0][lo:hi]),
                                  out=_p(out), weight=_p(d[2]), bias=_p(d[3]), stats=_p(d[1]), ext=C.cast(C.pointer(ext), C.c_void_p)))
@@ -467,7 +488,7 @@ def test_end_conv_with_its_own_statistics_matches_oracle(gpu, B, H, W):
     if B > 1:
         assert np.array_equal(run(B // 2, B), got[B // 2:])                    # a sample's numbers do not depend on its neighbours
     with pytest.raises(_lib.SbcError):                                           # shapes the kernel does not take are refused, not mangled
-        out = torch.zeros(2, 8, 8, 2, device='cuda')
+        out = _out((2, 8, 8, 2), fill=0.0)
         ext = _lib.sbc_endconv(sigmas=_p(d[4]), labels=_p(d[5]))
         _launch(gpu, _lib.sbc_op(kind=P.END_CONV, flags=P.PRO_NORM_SELF, B=2, H=8, W=8, cin=32, cout=2, ksize=3, dil=1, in_=_p(d[0]), out=_p(out),
                                  weight=_p(d[2]), bias=_p(d[3]), stats=_p(d[1]), ext=C.cast(C.pointer(ext), C.c_void_p)))
@@ -490,7 +511,7 @@ def test_f16x2_range_flag(gpu, wino):
     for peak, expect in ((15000.0, 0), (17000.0, 1)):
         x = rng.standard_normal((B, H, W, c)).astype(F32)
         x[1, 7, 9, 3] = peak
-        out = torch.full((B, H, W, c), float('nan'), dtype=torch.float32, device='cuda')
+        out = _out((B, H, W, c), 'out', must_write=not expect)         # (beyond the limit the numbers may overflow: the flag says so)
         dx = _dev(torch, x)
         op = _lib.sbc_op(kind=P.CONV, flags=P.CONV_F16X2, B=B, H=H, W=W, cin=c, cout=c, ksize=3, dil=1, in_=_p(dx), out=_p(out),
                          weight_split=_p(wx))
@@ -539,7 +560,7 @@ def test_conv_pair_matches_oracle(gpu, case, mode):
         ref = x + O.conv2d(round_fp16(O.elu(t)), round_fp16(w2), None, 1).transpose(0, 2, 3, 1)
     dx = _dev(torch, x)
     d1, d2 = _dev(torch, pack(w1).view(np.float32)), _dev(torch, pack(w2).view(np.float32))
-    out = torch.full((B, H, W, Cc), float('nan'), dtype=torch.float32, device='cuda')
+    out = _out((B, H, W, Cc))
     op = _lib.sbc_op(kind=P.CONV_PAIR, flags=flag, B=B, H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1, in_=_p(dx), out=_p(out),
                      weight_split=_p(d1), weight2_split=_p(d2))
     _launch(gpu, op)
@@ -549,13 +570,14 @@ def test_conv_pair_matches_oracle(gpu, case, mode):
     assert rel_err(conv_part, ref_part) < tol
     assert _lib.range_flag() == 0
     # the two launches it replaces
-    mid = torch.empty_like(out)
-    out2 = torch.empty_like(out)
+    mid = _out(x.shape, 'mid')
+    out2 = _out(x.shape, 'out2')
     a = _lib.sbc_op(kind=P.CONV, flags=flag | P.PRO_ELU, B=B, H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1, in_=_p(dx), out=_p(mid),
                     weight_split=_p(d1))
     b = _lib.sbc_op(kind=P.CONV, flags=flag | P.PRO_ELU, B=B, H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1, in_=_p(mid), out=_p(out2),
                     weight_split=_p(d2), res1=_p(dx))
     _launch(gpu, a)
+    _G.freeze(mid)                                                  # an output of the first launch, an input of the second
     _launch(gpu, b)
     assert rel_err(got - x, out2.cpu().numpy() - x) < tol
     if W == 16 and Cc == 32 and B * (H // 8) >= 1024:
@@ -565,7 +587,7 @@ def test_conv_pair_matches_oracle(gpu, case, mode):
         for lo in list(range(0, B, piece))[:6]:
             hi = min(lo + piece, B)
             assert (hi - lo) * (H // 8) < 1024
-            part = torch.full((hi - lo, H, W, Cc), float('nan'), dtype=torch.float32, device='cuda')
+            part = _out((hi - lo, H, W, Cc))
             sub = _lib.sbc_op(kind=P.CONV_PAIR, flags=flag, B=hi - lo, H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1, in_=_p(dx[lo:hi]),
                               out=_p(part), weight_split=_p(d1), weight2_split=_p(d2))
             _launch(gpu, sub)
@@ -607,7 +629,7 @@ def test_conv_pool_matches_oracle(gpu, B, H, stage, mode):
         res2 = rng.standard_normal((B, H, W, Cc)).astype(F32)
         ref = ref + (res2 + O.elu(res1))
     dx, dw = _dev(torch, x), _dev(torch, pack(w).view(np.float32))
-    out = torch.full((B, H, W, Cc), float('nan'), dtype=torch.float32, device='cuda')
+    out = _out((B, H, W, Cc))
     op = _lib.sbc_op(kind=P.CONV_POOL, flags=flags | mflag, B=B, H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1, in_=_p(dx), out=_p(out),
                      weight_split=_p(dw))
     keep = []
@@ -620,9 +642,10 @@ def test_conv_pool_matches_oracle(gpu, B, H, stage, mode):
     assert rel_err(got - (ref - conv_ref), conv_ref) < tol            # (the residual operands must not mask the convolution's error)
     assert _lib.range_flag() == 0
     # the two launches it replaces
-    pooled = torch.empty_like(out)
-    out2 = torch.empty_like(out)
+    pooled = _out(x.shape, 'pooled')
+    out2 = _out(x.shape, 'out2')
     _launch(gpu, _lib.sbc_op(kind=P.MAXPOOL5, flags=P.PRO_ELU if elu else 0, B=B, H=H, W=W, cin=Cc, cout=Cc, in_=_p(dx), out=_p(pooled)))
+    _G.freeze(pooled)
     dww = _dev(torch, packw(w).view(np.float32))
     b = _lib.sbc_op(kind=P.CONV, flags=(flags & P.EPI_RES1_ELU) | mflag, B=B, H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1, in_=_p(pooled),
                     out=_p(out2), weight_split=_p(dw), weight_wino_split=_p(dww))
@@ -651,11 +674,11 @@ def test_direct_conv_writes_tile_moments_in_f16w(gpu, B, H, W):
     res = rng.standard_normal((B, H, W, Cc)).astype(F32)
     w = (rng.standard_normal((Cc, Cc, 3, 3)) / np.sqrt(9 * Cc)).astype(F32)
     bias = (0.3 * rng.standard_normal(Cc)).astype(F32)
-    d = {k: _dev(torch, a) for k, a in dict(x=x, res=res, w=pack_conv_weight_f16(w).view(np.float32), ww=pack_conv_weight_winograd_f16(w).view(np.float32),
+    d = {k: _dev(torch, a, k) for k, a in dict(x=x, res=res, w=pack_conv_weight_f16(w).view(np.float32), ww=pack_conv_weight_winograd_f16(w).view(np.float32),
                                               b=bias).items()}
-    out = torch.full((B, H, W, Cc), float('nan'), dtype=torch.float32, device='cuda')
+    out = _out((B, H, W, Cc))
     nt = H * W // 128
-    pm = torch.full((B, nt, Cc, 2), float('nan'), dtype=torch.float32, device='cuda')
+    pm = _out((B, nt, Cc, 2))
     # (the Winograd form rides along as the host binds it: the f16w dispatch must not take it)
     op = _lib.sbc_op(kind=P.CONV, flags=P.CONV_F16W | P.PRO_ELU | P.EPI_MOMENTS_OUT, B=B, H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1, in_=_p(d['x']),
                      out=_p(out), bias=_p(d['b']), res1=_p(d['res']), weight_split=_p(d['w']), weight_wino_split=_p(d['ww']), aux=_p(pm))
@@ -670,7 +693,7 @@ def test_direct_conv_writes_tile_moments_in_f16w(gpu, B, H, W):
     assert np.abs(gm[..., 0] - tiles.mean(2)).max() < 1e-5 * max(1.0, np.abs(tiles.mean(2)).max())
     assert rel_err(gm[..., 1], ((tiles - tiles.mean(2, keepdims=True)) ** 2).sum(2)) < 1e-5
     # the same launch without moments: the same output, bit for bit
-    out2 = torch.empty_like(out)
+    out2 = _out(x.shape, 'out2')
     op.flags, op.aux, op.out = P.CONV_F16W | P.PRO_ELU, None, _p(out2)
     _launch(gpu, op)
     assert torch.equal(out, out2)
@@ -697,13 +720,13 @@ def test_direct_conv_with_norm_prologue_and_tile_moments(gpu, B):
     v = O.elu((x - st[:, None, None, 0]) * st[:, None, None, 1] + st[:, None, None, 2])
     nref = min(B, 4)
     ref = O.conv2d(v[:nref].transpose(0, 3, 1, 2), w, bias, 1).transpose(0, 2, 3, 1) + res[:nref]
-    d = {k: _dev(torch, a) for k, a in dict(x=x, res=res, st=st, b=bias, w=pack_conv_weight_f16x2(w).view(np.float32),
+    d = {k: _dev(torch, a, k) for k, a in dict(x=x, res=res, st=st, b=bias, w=pack_conv_weight_f16x2(w).view(np.float32),
                                               ww=pack_conv_weight_winograd_f16x2(w).view(np.float32)).items()}
     nt = H * W // 128
 
     def run(lo, hi, moments=True):
-        out = torch.full((hi - lo, H, W, Cc), float('nan'), dtype=torch.float32, device='cuda')
-        pm = torch.full((hi - lo, nt, Cc, 2), float('nan'), dtype=torch.float32, device='cuda')
+        out = _out((hi - lo, H, W, Cc))
+        pm = _out((hi - lo, nt, Cc, 2))
         op = _lib.sbc_op(kind=P.CONV, flags=P.CONV_F16X2 | P.PRO_NORM | P.PRO_ELU | (P.EPI_MOMENTS_OUT if moments else 0), B=hi - lo, H=H, W=W, cin=Cc, cout=Cc,
                          ksize=3, dil=1, in_=_p(d['x'][lo:hi]), out=_p(out), stats=_p(d['st'][lo:hi]), bias=_p(d['b']), res1=_p(d['res'][lo:hi]),
                          weight_split=_p(d['w']), weight_wino_split=_p(d['ww']), aux=_p(pm) if moments else None)
@@ -746,11 +769,11 @@ def test_res_block_matches_oracle(gpu, B):
     s2 = inorm_stats(t, *agb2)
     main = O.conv2d(O.elu(norm(t, s2)).transpose(0, 3, 1, 2), w2, b2, 1).transpose(0, 2, 3, 1)
     ref = x + main
-    d = {k: _dev(torch, a) for k, a in dict(x=x, s1=s1, w1=pack_conv_weight_f16x2(w1).view(np.float32),
+    d = {k: _dev(torch, a, k) for k, a in dict(x=x, s1=s1, w1=pack_conv_weight_f16x2(w1).view(np.float32),
                                               w2=pack_conv_weight_f16x2(w2).view(np.float32), b1=b1, b2=b2,
                                               n2=np.concatenate(agb2)).items()}
-    out = torch.full((B, H, W, Cc), float('nan'), dtype=torch.float32, device='cuda')
-    pm = torch.full((B, 8, Cc, 2), float('nan'), dtype=torch.float32, device='cuda')
+    out = _out((B, H, W, Cc))
+    pm = _out((B, 8, Cc, 2))
     op = _lib.sbc_op(kind=P.RES_BLOCK, flags=P.CONV_F16X2 | P.EPI_MOMENTS_OUT, B=B, H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1,
                      in_=_p(d['x']), out=_p(out), stats=_p(d['s1']), weight_split=_p(d['w1']), weight2_split=_p(d['w2']),
                      bias=_p(d['b1']), bias2=_p(d['b2']), norm2=_p(d['n2']), aux=_p(pm))
@@ -766,17 +789,19 @@ def test_res_block_matches_oracle(gpu, B):
     assert rel_err(gm[..., 1], ((tiles - tiles.mean(2, keepdims=True)) ** 2).sum(2)) < 1e-5
     # the records it replaces: conv (norm, ELU) -> statistics -> conv (norm, ELU, + x)
     wino = [_dev(torch, pack_conv_weight_winograd_f16x2(w).view(np.float32)) for w in (w1, w2)]
-    tt, st2, out2 = torch.empty_like(out), torch.empty((B, 3, Cc), dtype=torch.float32, device='cuda'), torch.empty_like(out)
+    tt, st2, out2 = _out(x.shape, 'tt'), _out((B, 3, Cc), 'st2'), _out(x.shape, 'out2')
     fl = P.CONV_F16X2 | P.PRO_NORM | P.PRO_ELU
     _launch(gpu, _lib.sbc_op(kind=P.CONV, flags=fl, B=B, H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1, in_=_p(d['x']), out=_p(tt),
                              stats=_p(d['s1']), bias=_p(d['b1']), weight_split=_p(d['w1']), weight_wino_split=_p(wino[0])))
+    _G.freeze(tt)
     _launch(gpu, _lib.sbc_op(kind=P.INORM_STATS, B=B, H=H, W=W, cin=Cc, cout=Cc, in_=_p(tt), out=_p(st2), weight=_p(d['n2'])))
+    _G.freeze(st2)
     _launch(gpu, _lib.sbc_op(kind=P.CONV, flags=fl, B=B, H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1, in_=_p(tt), out=_p(out2),
                              stats=_p(st2), bias=_p(d['b2']), res1=_p(d['x']), weight_split=_p(d['w2']), weight_wino_split=_p(wino[1])))
     assert rel_err(got - x, out2.cpu().numpy() - x) < TOL
     # batch independence, bit for bit: sample 0 alone
     if B > 1:
-        out1 = torch.empty((1, H, W, Cc), dtype=torch.float32, device='cuda')
+        out1 = _out((1, H, W, Cc), 'out1')
         op.B, op.out, op.aux, op.flags = 1, _p(out1), None, P.CONV_F16X2
         _launch(gpu, op)
         assert torch.equal(out1[0], out[0])
@@ -808,11 +833,11 @@ def test_winograd_variants_are_accurate_and_batch_size_independent(gpu, cin, cou
     ws, ww = _dev(torch, pk(w).view(np.float32)), _dev(torch, pkw(w).view(np.float32))
     wd = torch.from_numpy(w).cuda().double()
     for H, W, sizes in ((8, 2, (2400, 1000, 100)), (16, 4, (600, 50)), (32, 8, (300, 10))):
-        x = torch.randn(sizes[0], H, W, cin, device='cuda', generator=torch.Generator('cuda').manual_seed(H)) * 1.5 + 0.3
+        x = _dev(torch, torch.randn(sizes[0], H, W, cin, device='cuda', generator=torch.Generator('cuda').manual_seed(H)) * 1.5 + 0.3, 'x %dx%d' % (H, W))
         ref = torch.nn.functional.conv2d(torch.nn.functional.elu(x).permute(0, 3, 1, 2).double(), wd, padding=1).permute(0, 2, 3, 1)
         outs = []
         for B in sizes:
-            out = torch.full((B, H, W, cout), float('nan'), dtype=torch.float32, device='cuda')
+            out = _out((B, H, W, cout))
             op = _lib.sbc_op(kind=P.CONV, flags=flag | P.PRO_ELU, B=B, H=H, W=W, cin=cin, cout=cout, ksize=3, dil=1, in_=_p(x), out=_p(out),
                              weight_split=_p(ws))
             if wino:                                   # (without it: the direct kernels and their tile sizes, chosen by the pixel count)
@@ -869,7 +894,7 @@ def test_f16x2_is_fp32_class_at_every_input_scale(gpu, cin, cout, dil, B, H, W, 
     _lib.range_flag()
     for act_scale in (_pow2_scale(amax), 1.0):
         wx = _dev(torch, pack_conv_weight_f16x2(w, act_scale).view(np.float32))
-        out = torch.full((B, H, W, cout), float('nan'), dtype=torch.float32, device='cuda')
+        out = _out((B, H, W, cout), 'out', must_write=act_scale != 1.0 or log2_scale == 0)   # (else: within tolerance OR flagged)
         op = _lib.sbc_op(kind=P.CONV, flags=P.CONV_F16X2 | (P.PRO_ELU if elu else 0), B=B, H=H, W=W, cin=cin, cout=cout, ksize=3,
                          dil=dil, in_=_p(dx), out=_p(out), weight_split=_p(wx))
         if wino:
@@ -903,15 +928,18 @@ def test_f16x2_library_calibration_sets_the_layer_scales(gpu, log2_scale):
     w1 = np.abs(rng.standard_normal((c, c, 3, 3)) / 17 * 2.0 ** -7).astype(F32)   # positive: the intermediate stays where ELU is the identity
     w2 = (rng.standard_normal((c, c, 3, 3)) / 17).astype(F32)
     dx = _dev(torch, x)
-    dw0, dw0w = _dev(torch, pack_conv_weight_f16x2(w0).view(F32)), _dev(torch, pack_conv_weight_winograd_f16x2(w0).view(F32))
-    dw1, dw2 = _dev(torch, pack_conv_weight_f16x2(w1).view(F32)), _dev(torch, pack_conv_weight_f16x2(w2).view(F32))
-    o0 = torch.full((B, H, W, c), float('nan'), dtype=torch.float32, device='cuda')
-    o1 = torch.full((B, H, W, c), float('nan'), dtype=torch.float32, device='cuda')
+    # (in-out: sbc_f16x2_calibrate writes the trailers of the weight forms)
+    dw0, dw0w = _dev(torch, pack_conv_weight_f16x2(w0).view(F32), 'w0', True), _dev(torch, pack_conv_weight_winograd_f16x2(w0).view(F32), 'w0 wino', True)
+    dw1, dw2 = _dev(torch, pack_conv_weight_f16x2(w1).view(F32), 'w1', True), _dev(torch, pack_conv_weight_f16x2(w2).view(F32), 'w2', True)
+    o0 = _out((B, H, W, c))
+    o1 = _out((B, H, W, c))
     ops = [_lib.sbc_op(kind=P.CONV, flags=P.CONV_F16X2 | P.PRO_ELU, B=B, H=H, W=W, cin=c, cout=c, ksize=3, dil=1, in_=_p(dx),
                        out=_p(o0), weight_split=_p(dw0), weight_wino_split=_p(dw0w)),
            _lib.sbc_op(kind=P.CONV_PAIR, flags=P.CONV_F16X2, B=B, H=H, W=W, cin=c, cout=c, ksize=3, dil=1, in_=_p(dx),
                        out=_p(o1), weight_split=_p(dw1), weight2_split=_p(dw2))]
     _lib.calibrate_f16x2(ops, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    _G.check(written=False)                                         # (the pass runs the records on their first sample only)
     assert _lib.range_flag() == 0                                     # the pass clears what it raised itself
     v = dx                                                            # (positive inputs: ELU is the identity)
     t = _f64_conv(torch, v, w1, 1).float()
@@ -950,12 +978,14 @@ def test_res_block_is_calibrated_and_guarded(gpu, log2_scale):
     norm = lambda v, st: (v - st[:, None, None, 0]) * st[:, None, None, 1] + st[:, None, None, 2]
     t = O.conv2d(O.elu(norm(x, s1)).transpose(0, 3, 1, 2), w1, b1, 1).transpose(0, 2, 3, 1)
     main = O.conv2d(O.elu(norm(t, inorm_stats(t, *agb2))).transpose(0, 3, 1, 2), w2, b2, 1).transpose(0, 2, 3, 1)
-    d = {k: _dev(torch, a) for k, a in dict(x=x, s1=s1, w1=pack_conv_weight_f16x2(w1).view(np.float32),
+    d = {k: _dev(torch, a, k, inout=k in ('w1', 'w2')) for k, a in dict(x=x, s1=s1, w1=pack_conv_weight_f16x2(w1).view(np.float32),
                                               w2=pack_conv_weight_f16x2(w2).view(np.float32), b1=b1, b2=b2, n2=np.concatenate(agb2)).items()}
-    out = torch.full((B, H, W, c), float('nan'), dtype=torch.float32, device='cuda')
+    out = _out((B, H, W, c), 'out', must_write=False)                 # (the last launch overflows on purpose; the comparisons catch a NaN)
     op = _lib.sbc_op(kind=P.RES_BLOCK, flags=P.CONV_F16X2, B=B, H=H, W=W, cin=c, cout=c, ksize=3, dil=1, in_=_p(d['x']), out=_p(out),
                      stats=_p(d['s1']), weight_split=_p(d['w1']), weight2_split=_p(d['w2']), bias=_p(d['b1']), bias2=_p(d['b2']), norm2=_p(d['n2']))
     _lib.calibrate_f16x2([op], torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    _G.check()
     assert _lib.range_flag() == 0
     v1 = np.abs(O.elu(norm(x, s1))[0]).max()
     v2 = np.abs(O.elu(norm(t, inorm_stats(t, *agb2)))[0]).max()
@@ -1005,7 +1035,7 @@ def test_persistent_grid_width_does_not_change_results(gpu):
                                  (P.RES_BLOCK, 32, 64, 16, 300)):
         x = _dev(torch, (rng.standard_normal((Bb, Hh, Ww, cc)) * 1.5 + 0.3).astype(F32))
         w = [_dev(torch, pack_conv_weight_f16x2((rng.standard_normal((cc, cc, 3, 3)) / np.sqrt(9 * cc)).astype(F32)).view(np.float32)) for _ in range(2)]
-        out = torch.empty_like(x)
+        out = _out(tuple(x.shape))
         op = _lib.sbc_op(kind=kind, flags=P.CONV_F16X2 | (P.PRO_ELU if kind in (P.CONV, P.CONV_POOL) else 0), B=Bb, H=Hh, W=Ww, cin=cc, cout=cc,
                          ksize=3, dil=1, in_=_p(x), out=_p(out), weight_split=_p(w[0]))
         if kind in (P.CONV_PAIR, P.RES_BLOCK):
@@ -1108,7 +1138,7 @@ def test_chain_matches_oracle(gpu, Cc, H, W, B, blocks):
                 ch.w3[k], ch.bias3[k] = dev(pack_conv_weight_f16x2(ex['w3']).view(np.float32)), dev(ex['b3'])
 
     def run(xin):
-        out = torch.full(tuple(xin.shape), float('nan'), dtype=torch.float32, device='cuda')
+        out = _out(tuple(xin.shape))
         op = _lib.sbc_op(kind=P.CHAIN, flags=P.CONV_F16X2, B=xin.shape[0], H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1, in_=_p(xin), out=_p(out),
                          ext=C.cast(C.pointer(ch), C.c_void_p))
         _launch(gpu, op)
@@ -1161,7 +1191,7 @@ def test_chain_full_and_half_groups_agree(gpu, Cc, blocks):
     dx = _dev(torch, x)
 
     def run(xin):
-        out = torch.full(tuple(xin.shape), float('nan'), dtype=torch.float32, device='cuda')
+        out = _out(tuple(xin.shape))
         op = _lib.sbc_op(kind=P.CHAIN, flags=P.CONV_F16X2, B=xin.shape[0], H=H, W=W, cin=Cc, cout=Cc, ksize=3, dil=1, in_=_p(xin), out=_p(out),
                          ext=C.cast(C.pointer(ch), C.c_void_p))
         _launch(gpu, op)
@@ -1201,7 +1231,7 @@ def test_conv_down_matches_oracle(gpu, cin, cout, H, W, B):
     db3, db1 = _dev(torch, b3), _dev(torch, b1)
 
     def run(n):
-        out = torch.full((n, H // 2, W // 2, cout), float('nan'), dtype=torch.float32, device='cuda')
+        out = _out((n, H // 2, W // 2, cout))
         op = _lib.sbc_op(kind=P.CONV_DOWN, flags=P.CONV_F16X2, B=n, H=H, W=W, cin=cin, cout=cout, ksize=3, dil=1, in_=_p(da), out=_p(out),
                          res1=_p(dx), stats=_p(dst), weight_split=_p(d3), weight2_split=_p(d1), bias=_p(db3), bias2=_p(db1))
         _launch(gpu, op)

@@ -1191,3 +1191,170 @@ def test_trained_checkpoint_matches_reference_golden(trained_state, mode):
                 sc.append(float(net._wdev[off + w.shape[2] * w.shape[3] * w.shape[0] * w.shape[1]].item()))
         lg = np.log2(np.asarray(sc))
         print('f16x2 act_scale exponents over %d layers: min %d median %d max %d' % (len(sc), lg.min(), np.median(lg), lg.max()))
+
+
+# ---- the planned network inside guarded slots ---------------------------------------------------------------------------------
+# The records of a BoundScore are ctypes structs whose pointers lead into bound.slots (x and out are views of two of them), the
+# labels and the shared weight image.  `_remap` moves every pointer that falls inside one of the plan's own tensors to the same
+# offset inside a guarded replacement of EXACTLY the size the plan computed (B * slot_elems[i] floats between pads, tests/guarded.py),
+# so a launch that reads or writes past the slot the planner gave it meets a pad instead of allocator slack.  Same records, same
+# kernels, other addresses: the score is bit-identical to the unguarded run.
+
+def _remap(ops, old_tensors, guarded_tensors):
+    """Copies of ``ops`` (and of the END_CONV records' ``ext``) with every pointer field that falls inside ``old_tensors[i]``
+    rewritten to the same byte offset inside ``guarded_tensors[i]``.  Returns (records, structs to keep alive)."""
+    from score_based_channels_amd import _lib, plan as P
+    spans = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), g.data_ptr()) for t, g in zip(old_tensors, guarded_tensors)]
+    assert all(t.numel() * t.element_size() == g.numel() * g.element_size() for t, g in zip(old_tensors, guarded_tensors))
+
+    def move(struct, skip=()):
+        for name, ctype, *_ in struct._fields_:
+            v = getattr(struct, name) if ctype is C.c_void_p and name not in skip else None
+            for lo, hi, new in spans if v else ():
+                if lo <= v < hi:
+                    setattr(struct, name, new + (v - lo))
+                    break
+    recs, keep = [], []
+    for o in ops:
+        r = _lib.sbc_op.from_buffer_copy(o)
+        move(r, skip=('ext',))
+        if r.kind == P.END_CONV and r.ext:
+            e = _lib.sbc_endconv.from_buffer_copy(C.cast(r.ext, C.POINTER(_lib.sbc_endconv)).contents)
+            move(e)
+            keep.append(e)
+            r.ext = C.cast(C.pointer(e), C.c_void_p)
+        recs.append(r)
+    return recs, keep
+
+
+def _guarded_forward_equals_unguarded(net, B, nt, nr, lanes=None):
+    import torch
+    from guarded import Guard
+    from score_based_channels_amd import _lib
+    rng = np.random.default_rng(B * 100 + nt + nr)
+    x = torch.from_numpy(rng.standard_normal((B, nt, nr, 2)).astype(np.float32)).cuda()
+    labels = torch.from_numpy(rng.integers(0, 2311, B)).cuda()
+    stream = torch.cuda.current_stream().cuda_stream
+    bound = net.bind(B, nt, nr, lanes=lanes)
+    pl = bound.plan
+    assert [s.numel() for s in bound.slots] == [B * e for e in pl.slot_elems]
+    for s in bound.slots:
+        s.fill_(float('nan'))                             # (both runs start from the same slot contents)
+    bound.x.copy_(x)
+    bound.labels.copy_(labels)
+    plan = _lib.Plan(bound.ops, keepalive=bound)
+    plan.run(stream)
+    torch.cuda.synchronize()
+    want = bound.out.clone()
+    assert bool(torch.isfinite(want).all())
+    plan.close()
+    weights = net._wdev.clone()
+    # the same records inside guarded slots of exactly B * slot_elems[i] floats; slots are read and written, so in-out operands
+    # (+inf pads: a read past a slot's end enters the sums) that start as NaN except for x
+    g = Guard(torch)
+    nan = torch.full((1,), float('nan')).cuda()
+    slots = [g.inp('slot %d (%d x %d floats)' % (i, B, e), nan.expand(B * e), inout=True, pad=max(1024, e)) for i, e in enumerate(pl.slot_elems)]
+    slots[pl.x.slot].view(B, nt, nr, 2).copy_(x)
+    glabels = g.inp('labels', labels)
+    gsigmas = g.inp('sigmas', net.sigmas)
+    assert pl.x.slot != pl.out.slot
+    recs, keep = _remap(bound.ops, bound.slots + [bound.labels, net.sigmas], slots + [glabels, gsigmas])
+    moved = sum(getattr(a, n) != getattr(b, n) for a, b in zip(bound.ops, recs) for n in ('in_', 'out'))
+    assert moved == 2 * len(recs)                         # every record reads and writes a slot
+    plan = _lib.Plan(recs, keepalive=(g, keep, bound))
+    plan.run(stream)
+    torch.cuda.synchronize()
+    g.check()                                             # no pad touched, labels and sigmas unchanged
+    got = slots[pl.out.slot].view(B, nt, nr, 2)
+    assert torch.equal(got, want), float((got - want).abs().max())
+    assert torch.equal(net._wdev.view(torch.int32), weights.view(torch.int32))      # the weight image is read-only to a forward
+    plan.close()
+    if net.conv_mode == 'f16x2':
+        assert _lib.range_flag() == 0
+
+
+# the fusion switches as test_langevin_plan_composed_from_c_records varies them, and the shipped defaults
+_SWITCHES_OFF = dict(fold_stats=False, fuse_pairs=False, fuse_res=False, fuse_chain=False, fuse_down=False, fuse_end=False)
+_SWITCHES_PAIRS = dict(fold_stats=True, fuse_pairs=True, fuse_res=False, fuse_chain=False, fuse_down=False, fuse_end=False)
+_SWITCHES_CHAIN = dict(fold_stats=True, fuse_pairs=True, fuse_res=False, fuse_chain=True, fuse_down=False, fuse_end=False)
+
+
+@pytest.mark.parametrize('lanes', [True, False], ids=['lanes', 'sequential'])
+@pytest.mark.parametrize('mode,switches', [('f32', {}), ('f32', _SWITCHES_OFF), ('bf16x3', {}), ('bf16x3', _SWITCHES_OFF),
+                                           ('f16x2', {}), ('f16x2', _SWITCHES_OFF), ('f16x2', _SWITCHES_PAIRS), ('f16x2', _SWITCHES_CHAIN),
+                                           ('f16w', {}), ('f16w', _SWITCHES_OFF), ('f16w', _SWITCHES_PAIRS)],
+                         ids=lambda v: v if isinstance(v, str) else '+'.join(k for k, on in v.items() if on) or ('all-off' if v else 'default'))
+def test_forward_inside_guarded_slots_64x16(weights64, mode, switches, lanes):
+    """64 x 16, B = 3, every conv mode, the lane plan and the sequential plan, fusion switches on and off."""
+    from score_based_channels_amd.scorenet import ScoreNet
+    cfg, sd = weights64
+    net = ScoreNet(cfg, conv_mode=mode, **switches).cuda().load_state_dict(sd).eval()
+    _guarded_forward_equals_unguarded(net, 3, 64, 16, lanes=lanes)
+
+
+def test_forward_inside_guarded_slots_other_geometry(weights64):
+    """128 x 8, a geometry of test_forward_other_geometries_match_oracle (8-column images; like the other two of that list a power of
+    two in both directions, so the folded statistics stay on), B = 2."""
+    from score_based_channels_amd.config import default_config
+    from score_based_channels_amd.scorenet import ScoreNet
+    _, sd = weights64
+    net = ScoreNet(default_config(image_size=(8, 128))).cuda().load_state_dict(sd).eval()
+    _guarded_forward_equals_unguarded(net, 2, 128, 8)
+
+
+def test_forward_inside_guarded_slots_256x64():
+    """256 x 64, B = 1, the default mode."""
+    from score_based_channels_amd.config import default_config
+    from score_based_channels_amd.scorenet import ScoreNet
+    from score_based_channels_amd.weights import seeded_state_dict
+    cfg = default_config(image_size=(64, 256))
+    net = ScoreNet(cfg).cuda().load_state_dict(seeded_state_dict(cfg, 2024)).eval()
+    _guarded_forward_equals_unguarded(net, 1, 256, 64)
+
+
+def test_training_backward_inside_guarded_buffers(weights64):
+    """One reverse pass of train.TrainNet at a batch of two (loss, forward, every reverse operator, the weight gradients on their side
+    stream) with the records of its plan (TrainNet.records) moved into guarded replacements of the plan's slots, the gradient buffers,
+    tmp_a, the INORM_BWD and MAXPOOL5_BWD aux buffers and both weight-gradient scratches, each of exactly the trainer's size: no pad
+    touched, parameters unchanged, and gradients and losses bit-identical to the unguarded pass."""
+    import torch
+    from guarded import Guard
+    from score_based_channels_amd import _lib
+    from score_based_channels_amd.train import TrainNet
+    cfg, sd = weights64
+    gold = load_golden('train_dsm.npz')
+    B = 2
+    net = TrainNet(cfg, batch=B)
+    net.load_state_dict(sd)
+    args = (gold['x'][:B], gold['labels'][:B], gold['z'][:B])
+    want_loss = net.backward(*args).clone()
+    torch.cuda.synchronize()
+    want, params = net.grads.clone(), net.params.clone()
+    assert bool(torch.isfinite(want).all()) and float(want.abs().max()) > 0
+    named = ([('slot %d' % i, t) for i, t in enumerate(net.slots)] + [('gradient buffer %d' % i, t) for i, t in enumerate(net.gbuf.values())]
+             + [('pooled gradient %s' % k, t) for k, t in net.pool_grad.items()]
+             + [('tmp_a', net.tmp_a), ('inorm_aux', net.inorm_aux), ('pool_aux', net.pool_aux), ('scratch', net.scratch), ('scratch_main', net.scratch_main)])
+    g = Guard(torch)
+    old, new = [], []
+    for name, t in named:
+        old.append(t)
+        if t.dtype == torch.uint8:                        # the MAXPOOL5_BWD index bytes: sentinel byte pads
+            new.append(g.out(name, (t.numel(),), fill=0, dtype=torch.uint8, pad=max(4096, t.numel() // B)))
+        else:                                             # read and written, zeroed as the trainer allocates them; +inf pads
+            new.append(g.inp('%s (%d floats)' % (name, t.numel()), torch.zeros(t.numel()), inout=True, pad=max(1024, t.numel() // B)))
+    recs, keep = _remap(net.records('backward', replay=True), old, new)
+    spans = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in old]
+    for r in recs:
+        for name, ctype, *_ in r._fields_:
+            v = getattr(r, name) if ctype is C.c_void_p else None
+            assert not v or not any(lo <= v < hi for lo, hi in spans), name
+    net.grads.zero_()
+    net.loss_per_sample.zero_()
+    plan = _lib.Plan(recs, keepalive=(g, keep, net))
+    plan.run(torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    g.check()
+    assert torch.equal(net.grads.view(torch.int32), want.view(torch.int32)), float((net.grads - want).abs().max())
+    assert torch.equal(net.loss_per_sample, want_loss)
+    assert torch.equal(net.params.view(torch.int32), params.view(torch.int32))
+    plan.close()

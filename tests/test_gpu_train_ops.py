@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+import guarded
+from guarded import current as _G, dev as _dev, out as _out, pointer_fields
 
 pytestmark = pytest.mark.gpu
 
@@ -23,14 +25,26 @@ def gpu():
     return torch, _lib
 
 
-def _dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+# Every tensor a launch reads or writes is a view into a larger allocation with guarded margins (tests/guarded.py): `_dev` uploads an
+# operand between +inf pads (``inout``: one the operator is documented to write as well), `_out` hands out an output or a scratch
+# buffer of exactly the stated size between sentinel pads, and `_launch` checks after its synchronise that no pad and no input
+# changed and that the outputs were written.  One Guard per test.
+@pytest.fixture(autouse=True)
+def _guard(gpu):
+    yield guarded.begin(gpu[0])
+    guarded.end()
+
+
+def _scratch(n, B):
+    """A zeroed weight-gradient scratch of exactly ``n`` floats (arrival counters start at zero); pads of at least one sample's share."""
+    return _out(n, 'aux (wgrad scratch, %d floats)' % n, fill=0.0, pad=max(1024, -(-n // B)))
 
 
 def _launch(gpu, op):
     torch, _lib = gpu
     _lib.check(_lib.lib().sbc_op_launch(C.byref(op), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     torch.cuda.synchronize()
+    _G.check(touched=pointer_fields(op))
 
 
 def _p(t):
@@ -62,10 +76,10 @@ def _forward_stats(gpu, x, agb):
     torch, _lib = gpu
     from score_based_channels_amd import plan as P
     B, H, W, Cc = x.shape
-    st = torch.empty(B, 3, Cc, dtype=torch.float32, device='cuda')
+    st = _out((B, 3, Cc), 'stats')
     op = _lib.sbc_op(kind=P.INORM_STATS, B=B, H=H, W=W, cin=Cc, cout=Cc, in_=_p(x), out=_p(st), weight=_p(agb))
     _launch(gpu, op)
-    return st
+    return _G.freeze(st)                                # an output of this launch, an input of the next
 
 
 @pytest.mark.parametrize('elu,accum', [(False, False), (True, False), (True, True)])
@@ -77,7 +91,7 @@ def test_grad_add(gpu, elu, accum):
     g = rng.standard_normal(x.shape).astype(F32)
     o0 = rng.standard_normal(x.shape).astype(F32)
     ref = g * (np.where(x > 0, 1.0, np.exp(x.astype(np.float64))) if elu else 1.0) + (o0 if accum else 0.0)
-    dx, dg, do = _dev(torch, x), _dev(torch, g), _dev(torch, o0)
+    dx, dg, do = _dev(torch, x, 'x'), _dev(torch, g, 'grad'), _dev(torch, o0, 'out', inout=True)
     op = _lib.sbc_op(kind=P.GRAD_ADD, flags=(P.PRO_ELU if elu else 0) | (P.BWD_ACCUM if accum else 0), B=3, H=8, W=4, cin=32,
                      in_=_p(dx), grad=_p(dg), out=_p(do))
     _launch(gpu, op)
@@ -105,10 +119,10 @@ def test_inorm_backward_matches_autograd(gpu, C_, B, H, W, elu, accum):
     y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
     ref_dx = _nhwc(xt.grad) + (o0 if accum else 0.0)
     ref_dp = np.stack([p.grad.numpy() for p in pt])
-    dx, dagb, dg, do = _dev(torch, x), _dev(torch, agb), _dev(torch, g), _dev(torch, o0)
+    dx, dagb, dg, do = _dev(torch, x, 'x'), _dev(torch, agb, 'agb'), _dev(torch, g, 'grad'), _dev(torch, o0, 'out', inout=True)
     st = _forward_stats(gpu, dx, dagb)
-    aux = torch.empty(B * 6 * C_, dtype=torch.float32, device='cuda')
-    dp = torch.full((3, C_), float('nan'), dtype=torch.float32, device='cuda')
+    aux = _out(B * 6 * C_, 'aux (B*6*cin floats)', must_write=False)      # exactly the documented size
+    dp = _out((3, C_))
     op = _lib.sbc_op(kind=P.INORM_BWD, flags=(P.PRO_ELU if elu else 0) | (P.BWD_ACCUM if accum else 0), B=B, H=H, W=W, cin=C_,
                      in_=_p(dx), stats=_p(st), weight=_p(dagb), grad=_p(dg), out=_p(do), aux=_p(aux), wgrad=_p(dp))
     _launch(gpu, op)
@@ -130,8 +144,8 @@ def test_maxpool5_backward_matches_autograd(gpu, C_, B, H, W, elu, accum):
     y = torch.nn.functional.max_pool2d(torch.nn.functional.elu(xt) if elu else xt, 5, 1, 2)
     y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
     ref = _nhwc(xt.grad) + (o0 if accum else 0.0)
-    dx, dg, do = _dev(torch, x), _dev(torch, g), _dev(torch, o0)
-    aux = torch.empty(x.size, dtype=torch.uint8, device='cuda')
+    dx, dg, do = _dev(torch, x, 'x'), _dev(torch, g, 'grad'), _dev(torch, o0, 'out', inout=True)
+    aux = _out(x.size, 'aux (B*H*W*cin bytes)', fill=0, dtype=torch.uint8)   # exactly the documented size
     op = _lib.sbc_op(kind=P.MAXPOOL5_BWD, flags=(P.PRO_ELU if elu else 0) | (P.BWD_ACCUM if accum else 0), B=B, H=H, W=W,
                      cin=C_, in_=_p(dx), grad=_p(dg), out=_p(do), aux=_p(aux))
     _launch(gpu, op)
@@ -152,7 +166,7 @@ def test_upsample_backward_matches_autograd(gpu, C_, B, H, W, uh, uw, accum):
     y = torch.nn.functional.interpolate(u, size=(H, W), mode='bilinear', align_corners=True)
     y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
     ref = _nhwc(u.grad) + (o0 if accum else 0.0)
-    dg, do = _dev(torch, g), _dev(torch, o0)
+    dg, do = _dev(torch, g, 'grad'), _dev(torch, o0, 'out', inout=True)
     op = _lib.sbc_op(kind=P.UPSAMPLE_BWD, flags=P.BWD_ACCUM if accum else 0, B=B, H=H, W=W, cin=C_, up_h=uh, up_w=uw,
                      grad=_p(dg), out=_p(do))
     _launch(gpu, op)
@@ -165,7 +179,7 @@ def test_pool_backward(gpu):
     rng = np.random.default_rng(5)
     g = rng.standard_normal((3, 8, 4, 64)).astype(F32)
     dg = _dev(torch, g)
-    out = torch.full((3, 16, 8, 64), float('nan'), dtype=torch.float32, device='cuda')
+    out = _out((3, 16, 8, 64))
     op = _lib.sbc_op(kind=P.POOL_BWD, B=3, H=16, W=8, cin=64, grad=_p(dg), out=_p(out))
     _launch(gpu, op)
     ref = np.repeat(np.repeat(g, 2, axis=1), 2, axis=2) * 0.25
@@ -225,9 +239,9 @@ def test_conv_weight_gradient_matches_autograd(gpu, cin, cout, k, dil, B, H, W, 
     y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
     n_scr = int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, cin, cout, k))
     assert n_scr > 0
-    aux = torch.zeros(n_scr, dtype=torch.float32, device='cuda')
-    dw = torch.full((cout, cin, k, k), float('nan'), dtype=torch.float32, device='cuda')
-    db = torch.full((cout,), float('nan'), dtype=torch.float32, device='cuda')
+    aux = _scratch(n_scr, B)
+    dw = _out((cout, cin, k, k))
+    db = _out((cout,))
     op = _lib.sbc_op(kind=P.CONV_WGRAD, flags=flags, B=B, H=H, W=W, cin=cin, cout=cout, ksize=k, dil=dil, in_=_p(dx),
                      stats=_p(st), grad=_p(dg), aux=_p(aux), wgrad=_p(dw), bgrad=_p(db))
     _launch(gpu, op)
@@ -255,7 +269,7 @@ def test_device_weight_packing_matches_host_packer(gpu, cin, cout, k):
         wa = np.ascontiguousarray(w[:, :, ::-1, ::-1].transpose(1, 0, 2, 3)) if adj else w
         for wino in ((False, True) if k == 3 else (False,)):
             host = pack_conv_weight_winograd_split(wa) if wino else pack_conv_weight_split(wa)
-            out = torch.zeros(host.size, dtype=torch.int16, device='cuda')
+            out = _out(host.size, 'out (packed, adj %d wino %d)' % (adj, wino), fill=0, dtype=torch.int16)   # exactly the packed size
             op = _lib.sbc_op(kind=P.PACK_WEIGHT, flags=(P.PACK_ADJOINT if adj else 0) | (P.PACK_WINOGRAD if wino else 0),
                              cin=cin, cout=cout, ksize=k, in_=_p(dw), out=_p(out))
             _launch(gpu, op)
@@ -286,11 +300,13 @@ def test_input_gradient_is_a_conv_with_adjoint_weights(gpu, cin, cout, k, dil, B
     y = torch.nn.functional.conv2d(a, torch.from_numpy(w).double(), None, padding=dil * (k // 2), dilation=dil)
     y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
     ref = _nhwc(xt.grad) + (other if mode in ('elu_plus_other', 'elu_in_place') else 0.0)
-    dw, dg, dx, dother = _dev(torch, w), _dev(torch, g), _dev(torch, x), _dev(torch, other)
-    packed = torch.zeros(w.size * 3, dtype=torch.int16, device='cuda')
+    # (res1 == out with SBC_EPI_ELUGRAD: the gradient collected so far is read from the output buffer itself)
+    dw, dg, dx, dother = _dev(torch, w, 'w'), _dev(torch, g, 'grad'), _dev(torch, x, 'x'), _dev(torch, other, 'other', inout=mode == 'elu_in_place')
+    packed = _out(w.size * 3, 'packed', fill=0, dtype=torch.int16)
     op = _lib.sbc_op(kind=P.PACK_WEIGHT, flags=P.PACK_ADJOINT, cin=cin, cout=cout, ksize=k, in_=_p(dw), out=_p(packed))
     _launch(gpu, op)
-    out = dother if mode == 'elu_in_place' else torch.full((B, H, W, cin), float('nan'), dtype=torch.float32, device='cuda')
+    _G.freeze(packed)
+    out = dother if mode == 'elu_in_place' else _out((B, H, W, cin))
     op = _lib.sbc_op(kind=P.CONV, B=B, H=H, W=W, cin=cout, cout=cin, ksize=k, dil=dil, in_=_p(dg), out=_p(out),
                      weight_split=_p(packed))
     if mode != 'plain':
@@ -301,11 +317,12 @@ def test_input_gradient_is_a_conv_with_adjoint_weights(gpu, cin, cout, k, dil, B
     assert rel_err(out.cpu().numpy(), ref) < TOL
     if k == 3 and dil == 1:
         # the same through the Winograd kernel (adjoint Winograd form packed on the device)
-        wpacked = torch.zeros(cout * cin * 16 * 3, dtype=torch.int16, device='cuda')
+        wpacked = _out(cout * cin * 16 * 3, 'packed (Winograd)', fill=0, dtype=torch.int16)
         _launch(gpu, _lib.sbc_op(kind=P.PACK_WEIGHT, flags=P.PACK_ADJOINT | P.PACK_WINOGRAD, cin=cin, cout=cout, ksize=3,
                                  in_=_p(dw), out=_p(wpacked)))
+        _G.freeze(wpacked)
         if mode == 'elu_in_place':
-            dother.copy_(_dev(torch, other))
+            dother.copy_(torch.from_numpy(other))
         else:
             out.fill_(float('nan'))
         op.weight_wino_split = _p(wpacked)
@@ -335,10 +352,10 @@ def test_end_conv_backward_matches_autograd(gpu):
     dsig, dlab = _dev(torch, sigmas), _dev(torch, labels)
     st = _forward_stats(gpu, dx, dagb)
     ext = _lib.sbc_endconv(sigmas=_p(dsig), labels=_p(dlab))
-    aux = torch.zeros(int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, Cc, 2, 3)), dtype=torch.float32, device='cuda')
-    out = torch.full((B, H, W, Cc), float('nan'), dtype=torch.float32, device='cuda')
-    gw = torch.full((2, Cc, 3, 3), float('nan'), dtype=torch.float32, device='cuda')
-    gb = torch.full((2,), float('nan'), dtype=torch.float32, device='cuda')
+    aux = _scratch(int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, Cc, 2, 3)), B)
+    out = _out((B, H, W, Cc))
+    gw = _out((2, Cc, 3, 3))
+    gb = _out((2,))
     op = _lib.sbc_op(kind=P.END_CONV_BWD, B=B, H=H, W=W, cin=Cc, cout=2, ksize=3, dil=1, in_=_p(dx), stats=_p(st),
                      weight=_p(dwt), grad=_p(dg), out=_p(out), aux=_p(aux), wgrad=_p(gw), bgrad=_p(gb),
                      ext=C.cast(C.pointer(ext), C.c_void_p))
@@ -361,9 +378,9 @@ def test_begin_conv_backward_matches_autograd(gpu):
     y = torch.nn.functional.conv2d(2 * torch.from_numpy(x.transpose(0, 3, 1, 2).copy()).double() - 1, wt, bt, padding=1)
     y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
     dx, dg = _dev(torch, x), _dev(torch, g)
-    aux = torch.zeros(int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, 2, 32, 3)), dtype=torch.float32, device='cuda')
-    gw = torch.full((32, 2, 3, 3), float('nan'), dtype=torch.float32, device='cuda')
-    gb = torch.full((32,), float('nan'), dtype=torch.float32, device='cuda')
+    aux = _scratch(int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, 2, 32, 3)), B)
+    gw = _out((32, 2, 3, 3))
+    gb = _out((32,))
     op = _lib.sbc_op(kind=P.BEGIN_CONV_BWD, B=B, H=H, W=W, cin=2, cout=32, ksize=3, dil=1, in_=_p(dx), grad=_p(dg),
                      aux=_p(aux), wgrad=_p(gw), bgrad=_p(gb))
     _launch(gpu, op)
@@ -384,21 +401,20 @@ def test_dsm_perturb_and_loss_match_reference_formula(gpu):
     labels = np.array([0, 49, 17, 30, 5], np.int64)
     dx, dz, dsig, dlab = _dev(torch, x), _dev(torch, z), _dev(torch, sigmas), _dev(torch, labels)
     ext = _lib.sbc_dsm(sigmas=_p(dsig), labels=_p(dlab), noise=_p(dz), anneal_power=2.0)
-    pert = torch.empty(B, n, dtype=torch.float32, device='cuda')
-    noise = torch.empty(B, n, dtype=torch.float32, device='cuda')
+    pert, noise = _out((B, n), 'perturbed'), _out((B, n), 'noise')
     op = _lib.sbc_op(kind=P.DSM_PERTURB, B=B, H=H, W=W, cin=2, in_=_p(dx), out=_p(pert), aux=_p(noise),
                      ext=C.cast(C.pointer(ext), C.c_void_p))
     _launch(gpu, op)
     us = sigmas[labels][:, None]
     assert np.array_equal(noise.cpu().numpy(), z * us) and np.array_equal(pert.cpu().numpy(), x + z * us)
+    _G.freeze(noise)                                    # the loss launch reads it
     s = torch.from_numpy(rng.standard_normal((B, n)) / us.astype(np.float64)).requires_grad_(True)
     ust = torch.from_numpy(us.astype(np.float64))
     target = -1 / ust ** 2 * torch.from_numpy((z * us).astype(np.float64))
     per = 0.5 * ((s - target) ** 2).sum(dim=-1) * ust.squeeze() ** 2.0
     per.mean(dim=0).backward()
     ds_ = _dev(torch, s.detach().numpy().astype(F32))
-    loss = torch.empty(B, dtype=torch.float32, device='cuda')
-    dsc = torch.empty(B, n, dtype=torch.float32, device='cuda')
+    loss, dsc = _out((B,), 'loss'), _out((B, n), 'd(scores)')
     op = _lib.sbc_op(kind=P.DSM_LOSS, B=B, H=H, W=W, cin=2, in_=_p(ds_), grad=_p(noise), out=_p(loss), aux=_p(dsc),
                      ext=C.cast(C.pointer(ext), C.c_void_p))
     _launch(gpu, op)
@@ -408,6 +424,7 @@ def test_dsm_perturb_and_loss_match_reference_formula(gpu):
     dlab0 = _dev(torch, np.zeros(B, np.int64))
     ext2 = _lib.sbc_dsm(sigmas=_p(dsig), labels=_p(dlab0), seed=7, offset=3, anneal_power=2.0)
     outs = []
+    pert, noise = _out((B, n), 'perturbed (Philox)'), _out((B, n), 'noise (Philox)')
     for _ in range(2):
         op = _lib.sbc_op(kind=P.DSM_PERTURB, B=B, H=H, W=W, cin=2, in_=_p(dx), out=_p(pert), aux=_p(noise),
                          ext=C.cast(C.pointer(ext2), C.c_void_p))
@@ -429,10 +446,9 @@ def test_adam_ema_matches_torch_optimizer(gpu):
     pt = torch.from_numpy(p0.copy()).requires_grad_(True)
     opt = torch.optim.Adam([pt], lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), amsgrad=False, eps=1e-3)
     shadow = pt.data.clone()
-    dp = _dev(torch, p0)
-    state = torch.zeros(3, n, dtype=torch.float32, device='cuda')
-    state[2] = dp
-    step = torch.zeros(1, dtype=torch.int32, device='cuda')
+    dp = _dev(torch, p0, 'parameters', inout=True)
+    state = _dev(torch, np.stack([np.zeros(n, F32), np.zeros(n, F32), p0]), 'state', inout=True)
+    step = _dev(torch, np.zeros(1, np.int32), 'step')
     for k, g in enumerate(grads):
         pt.grad = torch.from_numpy(g.copy())
         opt.step()
@@ -442,6 +458,7 @@ def test_adam_ema_matches_torch_optimizer(gpu):
         op = _lib.sbc_op(kind=P.ADAM_EMA, in_=_p(dg), out=_p(dp), aux=_p(state), ext=C.cast(C.pointer(ext), C.c_void_p))
         _launch(gpu, op)
         step += 1
+        _G.resnap(step)
         assert np.max(np.abs(dp.cpu().numpy() - pt.data.numpy())) < 5e-7 * (k + 1), k
     assert np.max(np.abs(state[2].cpu().numpy() - shadow.numpy())) < 1e-6
     assert rel_err(state[0].cpu().numpy(), opt.state[pt]['exp_avg'].numpy()) < 1e-6
@@ -481,7 +498,9 @@ def test_batched_weight_packing_packs_every_entry_of_its_table(gpu):
     for off, w in src:
         flat[off:off + w.size] = w.ravel()
     dflat = _dev(torch, flat)
-    out = torch.full((d_off,), PATTERN, dtype=torch.int16, device='cuda')
+    d_off -= GUARD                                      # the last entry ends at the last element of `out`: exactly the table's extent
+    assert d_off == rows[-1][1] + want[-1][1].size
+    out = _out(d_off, 'out (all packed entries)', fill=PATTERN, dtype=torch.int16)
     table = _dev(torch, np.array(rows, np.int32))
     op = _lib.sbc_op(kind=P.PACK_WEIGHT, B=len(rows), cout=128, cin=128, ksize=3, in_=_p(dflat), out=_p(out), aux=_p(table))
     _launch(gpu, op)
@@ -490,7 +509,7 @@ def test_batched_weight_packing_packs_every_entry_of_its_table(gpu):
     for (off, host), row in zip(want, rows):
         assert np.array_equal(got[off:off + host.size], host), row
         covered[off:off + host.size] = True
-    assert (~covered).sum() == GUARD * (len(rows) + 1) and np.all(got[~covered] == PATTERN)
+    assert (~covered).sum() == GUARD * len(rows) and np.all(got[~covered] == PATTERN)
 
 
 def _dsm_reference(s, noise, us, power, B, gs):
@@ -518,8 +537,8 @@ def test_dsm_loss_paths(gpu, power, grad_scale, B, H, W):
     ref_loss, ref_ds = _dsm_reference(s, noise, us, power, B, grad_scale if grad_scale else 1.0)
     dsig, dlab, ds_, dnz = _dev(torch, sigmas), _dev(torch, labels), _dev(torch, s), _dev(torch, noise)
     ext = _lib.sbc_dsm(sigmas=_p(dsig), labels=_p(dlab), anneal_power=power, grad_scale=grad_scale)
-    loss = torch.full((B,), float('nan'), dtype=torch.float32, device='cuda')
-    dsc = torch.full((B, n), float('nan'), dtype=torch.float32, device='cuda')
+    loss = _out((B,))
+    dsc = _out((B, n))
     op = _lib.sbc_op(kind=P.DSM_LOSS, B=B, H=H, W=W, cin=2, in_=_p(ds_), grad=_p(dnz), out=_p(loss), aux=_p(dsc),
                      ext=C.cast(C.pointer(ext), C.c_void_p))
     _launch(gpu, op)
@@ -527,7 +546,7 @@ def test_dsm_loss_paths(gpu, power, grad_scale, B, H, W):
     assert rel_err(dsc.cpu().numpy(), ref_ds) < 1e-5
     for b in range(B):                                  # per sample: a small-sigma row must not hide behind a large one
         assert rel_err(dsc[b].cpu().numpy(), ref_ds[b]) < 1e-5, b
-    loss2 = torch.full((B,), float('nan'), dtype=torch.float32, device='cuda')
+    loss2 = _out((B,))
     op2 = _lib.sbc_op(kind=P.DSM_LOSS, B=B, H=H, W=W, cin=2, in_=_p(ds_), grad=_p(dnz), out=_p(loss2), aux=None,
                       ext=C.cast(C.pointer(ext), C.c_void_p))
     _launch(gpu, op2)
@@ -550,8 +569,8 @@ def test_dsm_perturb_philox_keying(gpu):
         dstep = _dev(torch, np.array([step], np.int32)) if step is not None else None
         ext = _lib.sbc_dsm(sigmas=_p(dsig), labels=_p(dlab), sample_id=_p(did), seed=seed, offset=offset, step=_p(dstep),
                            anneal_power=2.0)
-        pert = torch.full((B, n), float('nan'), dtype=torch.float32, device='cuda')
-        noise = torch.full((B, n), float('nan'), dtype=torch.float32, device='cuda')
+        pert = _out((B, n))
+        noise = _out((B, n))
         _launch(gpu, _lib.sbc_op(kind=P.DSM_PERTURB, B=B, H=H, W=W, cin=2, in_=_p(dx), out=_p(pert), aux=_p(noise),
                                  ext=C.cast(C.pointer(ext), C.c_void_p)))
         assert torch.equal(pert, noise)                 # x = 0, sigma = 1
@@ -588,9 +607,9 @@ def test_adam_ema_far_from_step_zero(gpu, t0, ema_mu, n):
     m = m0.astype(np.float64) + (g.astype(np.float64) - m0) * (1 - b1)
     v = v0.astype(np.float64) * b2 + (1 - b2) * g.astype(np.float64) ** 2
     p = p0 - (lr / (1 - b1 ** t)) * (m / (np.sqrt(v) / np.sqrt(1 - b2 ** t) + eps))
-    dp, dg = _dev(torch, p0), _dev(torch, g)
-    state = _dev(torch, np.stack([m0, v0, sh0]))
-    step = _dev(torch, np.array([t0], np.int32))
+    dp, dg = _dev(torch, p0, 'parameters', inout=True), _dev(torch, g, 'grad')
+    state = _dev(torch, np.stack([m0, v0, sh0]), 'state', inout=True)
+    step = _dev(torch, np.array([t0], np.int32), 'step')
     ext = _lib.sbc_adam(n=n, lr=lr, beta1=b1, beta2=b2, eps=eps, ema_mu=ema_mu, step=_p(step))
     _launch(gpu, _lib.sbc_op(kind=P.ADAM_EMA, in_=_p(dg), out=_p(dp), aux=_p(state), ext=C.cast(C.pointer(ext), C.c_void_p)))
     assert int(step.item()) == t0                       # the counter belongs to SBC_OP_STEP_INC
@@ -620,8 +639,8 @@ def test_maxpool5_backward_with_exact_ties(gpu, C_, B, H, W, flat, elu):
     ref = _nhwc(xt.grad)
     assert flat or np.mean(ref == 0) > 0.5              # ties and losers: most elements receive nothing
     dx, dg = _dev(torch, x), _dev(torch, g)
-    do = torch.full(x.shape, float('nan'), dtype=torch.float32, device='cuda')
-    aux = torch.empty(x.size, dtype=torch.uint8, device='cuda')
+    do = _out(x.shape)
+    aux = _out(x.size, 'aux (B*H*W*cin bytes)', fill=0, dtype=torch.uint8)   # exactly the documented size
     op = _lib.sbc_op(kind=P.MAXPOOL5_BWD, flags=P.PRO_ELU if elu else 0, B=B, H=H, W=W, cin=C_, in_=_p(dx), grad=_p(dg),
                      out=_p(do), aux=_p(aux))
     _launch(gpu, op)
@@ -657,9 +676,9 @@ def test_begin_conv_backward_at_other_images(gpu, B, H, W, rows):
     dx, dg = _dev(torch, x), _dev(torch, g)
     n_scr = int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, 2, 32, 3))
     assert n_scr == 16 + B * (H // rows) * (9 * 2 * 32 + 32)
-    aux = torch.zeros(n_scr, dtype=torch.float32, device='cuda')
-    gw = torch.full((32, 2, 3, 3), float('nan'), dtype=torch.float32, device='cuda')
-    gb = torch.full((32,), float('nan'), dtype=torch.float32, device='cuda')
+    aux = _scratch(n_scr, B)
+    gw = _out((32, 2, 3, 3))
+    gb = _out((32,))
     op = _lib.sbc_op(kind=P.BEGIN_CONV_BWD, B=B, H=H, W=W, cin=2, cout=32, ksize=3, dil=1, in_=_p(dx), grad=_p(dg),
                      aux=_p(aux), wgrad=_p(gw), bgrad=_p(gb))
     _launch(gpu, op)
@@ -696,10 +715,10 @@ def test_end_conv_backward_at_other_images_and_noise_sources(gpu, B, H, W, rows,
         ext = _lib.sbc_endconv(sigmas=_p(dsig), labels=_p(dlab))
     else:
         ext = _lib.sbc_endconv(sigma_of_step=_p(dsig), step=_p(dstep))
-    aux = torch.zeros(int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, Cc, 2, 3)), dtype=torch.float32, device='cuda')
-    out = torch.full((B, H, W, Cc), float('nan'), dtype=torch.float32, device='cuda')
-    gw = torch.full((2, Cc, 3, 3), float('nan'), dtype=torch.float32, device='cuda')
-    gb = torch.full((2,), float('nan'), dtype=torch.float32, device='cuda')
+    aux = _scratch(int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, Cc, 2, 3)), B)
+    out = _out((B, H, W, Cc))
+    gw = _out((2, Cc, 3, 3))
+    gb = _out((2,))
     op = _lib.sbc_op(kind=P.END_CONV_BWD, B=B, H=H, W=W, cin=Cc, cout=2, ksize=3, dil=1, in_=_p(dx), stats=_p(st),
                      weight=_p(dwt), grad=_p(dg), out=_p(out), aux=_p(aux), wgrad=_p(gw), bgrad=_p(gb),
                      ext=C.cast(C.pointer(ext), C.c_void_p))
@@ -735,10 +754,10 @@ def test_inorm_backward_edges(gpu, C_, B, H, W, offset):
     y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
     ref_dx, ref_dp = _nhwc(xt.grad), np.stack([p.grad.numpy() for p in pt])
     dx, dagb, dg = _dev(torch, x), _dev(torch, agb), _dev(torch, g)
-    do = torch.full(x.shape, float('nan'), dtype=torch.float32, device='cuda')
+    do = _out(x.shape)
     st = _forward_stats(gpu, dx, dagb)
-    aux = torch.empty(B * 6 * C_, dtype=torch.float32, device='cuda')
-    dp = torch.full((3, C_), float('nan'), dtype=torch.float32, device='cuda')
+    aux = _out(B * 6 * C_, 'aux (B*6*cin floats)', must_write=False)      # exactly the documented size
+    dp = _out((3, C_))
     op = _lib.sbc_op(kind=P.INORM_BWD, flags=P.PRO_ELU, B=B, H=H, W=W, cin=C_, in_=_p(dx), stats=_p(st), weight=_p(dagb),
                      grad=_p(dg), out=_p(do), aux=_p(aux), wgrad=_p(dp))
     _launch(gpu, op)
@@ -758,7 +777,7 @@ def test_pool_backward_shapes(gpu, C_, B, H, W):
     rng = np.random.default_rng(C_ + H)
     g = rng.standard_normal((B, H // 2, W // 2, C_)).astype(F32)
     dg = _dev(torch, g)
-    out = torch.full((B, H, W, C_), float('nan'), dtype=torch.float32, device='cuda')
+    out = _out((B, H, W, C_))
     _launch(gpu, _lib.sbc_op(kind=P.POOL_BWD, B=B, H=H, W=W, cin=C_, grad=_p(dg), out=_p(out)))
     assert np.array_equal(out.cpu().numpy(), (np.repeat(np.repeat(g, 2, axis=1), 2, axis=2) * 0.25).astype(F32))
 
@@ -773,7 +792,7 @@ def test_grad_add_shapes(gpu, C_, B, H, W, elu, accum):
     g = rng.standard_normal(x.shape).astype(F32)
     o0 = rng.standard_normal(x.shape).astype(F32)
     ref = g * (np.where(x > 0, 1.0, np.exp(x.astype(np.float64))) if elu else 1.0) + (o0 if accum else 0.0)
-    dx, dg, do = _dev(torch, x), _dev(torch, g), _dev(torch, o0)
+    dx, dg, do = _dev(torch, x, 'x'), _dev(torch, g, 'grad'), _dev(torch, o0, 'out', inout=True)
     op = _lib.sbc_op(kind=P.GRAD_ADD, flags=(P.PRO_ELU if elu else 0) | (P.BWD_ACCUM if accum else 0), B=B, H=H, W=W, cin=C_,
                      in_=_p(dx), grad=_p(dg), out=_p(do))
     _launch(gpu, op)
@@ -796,7 +815,7 @@ def test_upsample_backward_degenerate_windows(gpu, C_, B, H, W, uh, uw, accum):
     y = SA.bilinear_align_corners(u, (H, W))
     y.backward(torch.from_numpy(g.transpose(0, 3, 1, 2).copy()).double())
     ref = _nhwc(u.grad) + (o0 if accum else 0.0)
-    dg, do = _dev(torch, g), _dev(torch, o0)
+    dg, do = _dev(torch, g, 'grad'), _dev(torch, o0, 'out', inout=True)
     op = _lib.sbc_op(kind=P.UPSAMPLE_BWD, flags=P.BWD_ACCUM if accum else 0, B=B, H=H, W=W, cin=C_, up_h=uh, up_w=uw,
                      grad=_p(dg), out=_p(do))
     _launch(gpu, op)
@@ -809,11 +828,10 @@ def test_conv_weight_gradient_refuses_an_image_it_cannot_tile(gpu):
     torch, _lib = gpu
     from score_based_channels_amd import plan as P
     B, H, W, c = 2, 12, 4, 64
-    dx = torch.zeros(B, H, W, c, dtype=torch.float32, device='cuda')
-    dg = torch.zeros(B, H, W, c, dtype=torch.float32, device='cuda')
-    aux = torch.zeros(int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, c, c, 3)), dtype=torch.float32, device='cuda')
-    dw = torch.full((c, c, 3, 3), float('nan'), dtype=torch.float32, device='cuda')
-    db = torch.full((c,), float('nan'), dtype=torch.float32, device='cuda')
+    dx, dg = _dev(torch, np.zeros((B, H, W, c), F32), 'x'), _dev(torch, np.zeros((B, H, W, c), F32), 'grad')
+    aux = _scratch(int(_lib.lib().sbc_wgrad_scratch_floats(B, H, W, c, c, 3)), B)
+    dw = _out((c, c, 3, 3))
+    db = _out((c,))
     op = _lib.sbc_op(kind=P.CONV_WGRAD, flags=P.PRO_ELU, B=B, H=H, W=W, cin=c, cout=c, ksize=3, dil=1, in_=_p(dx), grad=_p(dg),
                      aux=_p(aux), wgrad=_p(dw), bgrad=_p(db))
     rc = _lib.lib().sbc_op_launch(C.byref(op), C.c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -822,3 +840,4 @@ def test_conv_weight_gradient_refuses_an_image_it_cannot_tile(gpu):
     with pytest.raises(_lib.SbcError, match='12x4'):
         _lib.check(rc)
     assert bool(torch.isnan(dw).all()) and bool(torch.isnan(db).all()) and float(aux.abs().max()) == 0.0
+    _G.check(written=False)

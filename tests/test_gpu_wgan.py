@@ -510,3 +510,45 @@ def test_a_callers_stream(fix, net):
     assert same_bits(zs.cpu().numpy(), g['z'])                               # the caller's latents are not written
     torch.cuda.synchronize()
     del keep
+
+
+# ---- a workspace of exactly sbc_wgan_workspace_floats(h, B) floats between guarded margins (tests/guarded.py) --------------------------
+class GuardedG(wgan.DCGAN_G_Ours):
+    """The generator with ``DeviceHandle._workspace_of`` overridden: every call gets a fresh workspace of EXACTLY the size the library
+    asked for, NaN-filled (the library promises nothing about what it holds), between pads of one per-sample stride."""
+    guard = None
+
+    def _workspace_of(self, n, dev):
+        f = _lib.lib().sbc_wgan_workspace_floats
+        assert int(n) == int(f(self._h, self.batch))
+        stride = int(f(self._h, self.batch + 1)) - int(n)
+        return self.guard.out('workspace (%d floats, B %d)' % (n, self.batch), (int(n),), must_write=False, pad=max(1024, stride))
+
+
+@pytest.mark.parametrize('B', [1, 5])
+@pytest.mark.parametrize('n_extra', [2, 0, 4])
+def test_exact_workspace_between_guards(fix, n_extra, B):
+    """sbc_wgan_run (one step) and sbc_wgan_generate at the fixture's depth and the depths of test_forward_other_depths: forward terms by
+    rule R (e_ref over the fixture's four samples), masks, no write outside the workspace, and the bits of the unguarded generator."""
+    from guarded import Guard
+    g, sd_fix = fix
+    assert int(g['n_extra']) == 2
+    sd = sd_fix if n_extra == 2 else wgan.seeded_state_dict(21, n_extra)
+    n = GuardedG([16, 64], 60, 2, 128, 1, n_extra).load_state_dict(sd).cuda().eval()
+    n.guard, n.batch = Guard(torch), B
+    idx = np.arange(B) % 4
+    full = [g[k] for k in ('z', 'Y', 'P', 'H')]
+    a = [v[idx] for v in full]
+    got = run(n, *a, 0.01, 1.0, 0.5, 1)
+    n.guard.check()
+    f64, f32 = O.forward_terms(sd, *full, F64), O.forward_terms(sd, *full, F32)
+    for k, name in (('gen', 'gen'), ('meas', 'meas'), ('reg', 'reg'), ('oracle', 'nmse')):
+        rule_r('n_extra %d B %d %s' % (n_extra, B, name), got[k] if k == 'gen' else got[k][0], f64[name][idx], e_of(f32[name], f64[name]))
+    assert_masks(got['masks'], [x[idx] for x in f64['pre']])
+    out = n(T(a[0]))
+    torch.cuda.synchronize()
+    n.guard.check()
+    assert same_bits(out.cpu().numpy(), got['gen'])
+    plain = run(make_net(sd), *a, 0.01, 1.0, 0.5, 1)
+    for k in ('z', 'm', 'v', 'gen', 'dG', 'meas', 'reg', 'oracle', 'z_full', 'g'):
+        assert same_bits(got[k], plain[k]), k

@@ -11,6 +11,8 @@ float64 directly; the kernel's masks may differ from float64's only within 1e-4 
 float64 UNDER THE KERNEL'S OWN MASKS; single backward launches are held to float64 on the kernel's own inputs.  Nothing is compared after
 RMSprop has accumulated: the optimiser is tested alone, bit for bit against the float32 formula.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -95,6 +97,27 @@ def forward_checks(what, st, f64, f32, twin):
                 rule_r('%s %s%d' % (what, kind, k), st[kind][k], r, f32[kind][k], twin[kind][k])
 
 
+class GuardedTrainer(wgan.Trainer):
+    """The trainer with ``DeviceHandle._workspace_of`` overridden: a workspace of EXACTLY sbc_wgan_trainer_workspace_floats(h, capacity)
+    floats, NaN-filled (the library promises nothing about what it holds), between pads of one per-sample stride (tests/guarded.py)."""
+    guard = None
+
+    def _workspace_of(self, n, dev):
+        from guarded import Guard
+        f = _lib.lib().sbc_wgan_trainer_workspace_floats
+        assert int(n) == int(f(self._h, self.capacity))
+        if self.guard is None:
+            self.guard = Guard(torch)
+            stride = int(f(self._h, self.capacity + 1)) - int(n)
+            self._ws = self.guard.out('trainer workspace (%d floats, capacity %d)' % (n, self.capacity), (int(n),), must_write=False,
+                                      pad=max(1024, stride))
+        return self._ws
+
+    def check_guards(self):
+        torch.cuda.synchronize()
+        self.guard.check()
+
+
 class Case:
     """a trainer at the reference's initial distributions, and what one critic and one generator iteration leave behind"""
 
@@ -102,7 +125,9 @@ class Case:
         self.n_extra, self.Br, self.Bf = n_extra, Br, Bf
         self.gsd, self.dsd = wgan.init_state_dicts(seed, n_extra)
         self.real, self.noise = inputs(Br, Bf, seed)
-        self.tr = wgan.Trainer(self.gsd, self.dsd, batch_size=max(Br, Bf))
+        # (both batches at the capacity in '4-4-extra1'; the real batch below it in '3-5-extra1'; the fake batch -- and with it the
+        # generator iteration -- below it in '5-3-extra1')
+        self.tr = GuardedTrainer(self.gsd, self.dsd, batch_size=max(Br, Bf))
 
     def critic(self, noise):
         """-> everything about one critic iteration from the trainer's CURRENT state"""
@@ -111,6 +136,7 @@ class Case:
         dsd = {k: (T.clamp(v) if TRAINABLE(k) else v) for k, v in dsd.items()}
         sq0 = {k: tr.tensor('d', k, 'square_avg') for k in dsd if TRAINABLE(k)}
         losses = tr.critic_step(self.real, noise).cpu().numpy()
+        tr.check_guards()
         got = {'losses': losses, 'gsd': gsd, 'dsd': dsd, 'sq0': sq0, 'g': stages(tr, 'g', 2 + n), 'd0': stages(tr, 'd0', n + 2), 'd1': stages(tr, 'd1', n + 2),
                'gen': tr.stage('g.gen').cpu().numpy(), 'grads': {k: tr.tensor('d', k, 'grad') for k in dsd if TRAINABLE(k)}}
         got['after'] = tr.state_dicts()
@@ -126,6 +152,7 @@ class Case:
         gsd, dsd = tr.state_dicts()
         sq0 = {k: tr.tensor('g', k, 'square_avg') for k in gsd if TRAINABLE(k)}
         loss = tr.generator_step(noise).cpu().numpy()
+        tr.check_guards()
         got = {'loss': loss, 'gsd': gsd, 'dsd': dsd, 'sq0': sq0, 'g': stages(tr, 'g', 2 + n), 'd1': stages(tr, 'd1', n + 2), 'gen': tr.stage('g.gen').cpu().numpy(),
                'dgen': tr.stage('g.dgen').cpu().numpy(), 'grads': {k: tr.tensor('g', k, 'grad') for k in gsd if TRAINABLE(k)}}
         got['after'] = tr.state_dicts()
@@ -138,7 +165,9 @@ class Case:
 
 
 # (n_extra, real batch, fake batch): the fixture geometry; unequal batches; B = 1 (statistics over H W alone); the other depths
-CASES = {'4-4-extra1': (1, 4, 4, 101), '3-5-extra1': (1, 3, 5, 102), '1-1-extra0': (0, 1, 1, 103), '2-2-extra2': (2, 2, 2, 104)}
+# ... and a fake batch below the trainer's capacity ('5-3': G, the critic's fake pass and the generator iteration on 3 of 5 samples' room)
+CASES = {'4-4-extra1': (1, 4, 4, 101), '3-5-extra1': (1, 3, 5, 102), '1-1-extra0': (0, 1, 1, 103), '2-2-extra2': (2, 2, 2, 104),
+         '5-3-extra1': (1, 5, 3, 106)}
 _cache = {}
 
 
@@ -305,7 +334,18 @@ def test_wgrad128_alone(ks, up, B, H, W):
     rng = np.random.default_rng(ks * 100 + H)
     draw = rng.standard_normal((B, 128, H, W)).astype(np.float32)
     inp = rng.standard_normal((B, 128, H >> up, W >> up)).astype(np.float32)
-    got = wgan.wgrad128(dev(draw), dev(inp), ks, up).cpu().numpy()
+    # operands between guarded margins, a scratch of exactly sbc_wgan_wgrad128_scratch_floats(...) floats (tests/guarded.py)
+    from guarded import Guard
+    g = Guard(torch)
+    n = int(_lib.lib().sbc_wgan_wgrad128_scratch_floats(B, H, W, ks))
+    assert n > 0
+    ddraw, dinp, dW = g.inp('draw', draw), g.inp('inp', inp), g.out('dW', (128, 128, ks, ks))
+    scratch = g.out('scratch (%d floats)' % n, (n,), must_write=False, pad=max(1024, -(-n // B)))
+    p = lambda t: C.c_void_p(t.data_ptr())                                  # noqa: E731
+    _lib.check(_lib.lib().sbc_wgan_wgrad128(p(ddraw), p(dinp), p(dW), p(scratch), B, H, W, ks, up, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()
+    g.check()
+    got = dW.cpu().numpy()
     alone('wgrad128<%d> up %d' % (ks, up), lambda d, a, dt: T.conv_wgrad(d, a, (128, 128, ks, ks), 1, ks // 2, up, dt), [draw, inp], got)
     assert same_bits(got, wgan.wgrad128(dev(draw), dev(inp), ks, up).cpu().numpy())
 
