@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SBC_ABI_VERSION 14
+#define SBC_ABI_VERSION 15
 
 typedef enum sbc_status {
     SBC_OK = 0,
@@ -237,7 +237,7 @@ typedef struct sbc_op {
     int32_t signal;              /* 0, or an event id 1 .. SBC_MAX_EVENTS: recorded on this record's lane right behind it */
     int32_t wait[2];             /* 0, or event ids this record's lane waits for in front of it; the id must be signalled by a record
                                     EARLIER in the list (of the same iteration).  The host that builds the list owns the hazards: a
-                                    record must not write what a concurrently running lane reads or writes (plan.assign_slots) */
+                                    record must not write what a concurrently running lane reads or writes (sbc_score_wiring_create shares storage accordingly) */
 } sbc_op;
 #define SBC_MAX_LANES 4
 #define SBC_MAX_EVENTS 64
@@ -436,9 +436,9 @@ int sbc_pack_conv_weight_split(const float* src, int32_t cout, int32_t cin, int3
 int sbc_pack_conv_weight_winograd_split(const float* src, int32_t cout, int32_t cin, uint16_t* dst);
 
 /* --- the whole score network behind one call (hosts that are not Python) -------------------------------
- * The Python host (score_based_channels_amd/plan.py, scorenet.py) wires NCSNv2Deepest.forward
- * (ncsnv2/models/ncsnv2.py:269-300) into ~150 sbc_op records, shares activation storage, packs the weights and binds
- * device memory.  sbc_score_create does all of that inside the library from the tensors of the reference checkpoint's
+ * NCSNv2Deepest.forward (ncsnv2/models/ncsnv2.py:269-300) becomes ~150 sbc_op records: the library wires them and shares
+ * activation storage between them (sbc_score_wiring_* below), a host packs the weights and binds device memory (the Python host:
+ * score_based_channels_amd/scorenet.py).  sbc_score_create does all of that inside the library from the tensors of the reference checkpoint's
  * `model_state` (names as in NCSNv2Deepest.state_dict(): "res2.0.conv2.conv.weight", "normalizer.alpha", ...; HOST
  * pointers, float32, torch layouts).  The handle owns its device memory (weights, activation slots for `batch` samples,
  * labels).  conv_mode: 0 = split-bf16 (fp32-accurate), 1 = fp32 MFMA, 2 = fp16 weights (SBC_CONV_F16W; every parameter is
@@ -476,7 +476,7 @@ typedef struct sbc_score_desc {
                                     (scorenet.DEFAULT_FUSE_END) */
 #define SBC_SCORE_SKIP_LANES 0x40 /* (ABI 14) the decoder's skip branches (refineK.adapt_convs.0) behind their anchor records on launch lane 1 (sbc_op.lane /
                                     signal / wait): for small batches, where the low-resolution launches are latency-bound -- what the Python host does for
-                                    batches of at most scorenet.SKIP_OVERLAP_MAX_T trajectories (plan.hoist_skip_branches; identical results) */
+                                    batches of at most scorenet.SKIP_OVERLAP_MAX_T trajectories (identical results) */
 typedef struct sbc_score sbc_score;
 int sbc_score_create(const sbc_score_desc* desc, const sbc_tensor_ref* tensors, int32_t n_tensors, sbc_score** out);
 int sbc_score_buffers(sbc_score* score, float** x, float** out, int64_t** labels);
@@ -484,6 +484,65 @@ int sbc_score_ops(sbc_score* score, const sbc_op** ops, int32_t* n_ops);
 int sbc_score_level_source(sbc_score* score, const float* sigma_of_step, const int32_t* step);
 int sbc_score_forward(sbc_score* score, void* stream);
 void sbc_score_destroy(sbc_score* score);
+
+/* --- the wiring of the score network, without a device (ABI 15) --------------------------------------------------
+ * Which records one score evaluation consists of, in which order and on which launch lane, and which logical tensors share a buffer:
+ * what sbc_score_create binds to device memory, for hosts that bind it themselves (score_based_channels_amd/plan.py reads it into
+ * its dataclasses).  Pure host code: none of the three calls initialises HIP.
+ *   sbc_score_wiring_create   wires what `desc` asks for -- unlike sbc_score_create it does not look at a conv_mode and does not drop
+ *                             SBC_SCORE_FOLD_STATS for arrays that are no powers of two; refusals (SBC_ERR_INVALID, sbc_last_error):
+ *                             Nt or Nr no multiple of 8, SBC_SCORE_SKIP_LANES with SBC_WIRING_OVERLAP, a skip branch that is not one
+ *                             contiguous run of records or reads what its anchor does not have yet, a missing anchor, a lane outside
+ *                             1 .. SBC_MAX_LANES-1, a third wait on one record, more than SBC_MAX_EVENTS events;
+ *   sbc_score_wiring_read     flat arrays owned by the handle (strings included), valid until sbc_score_wiring_destroy. */
+typedef struct sbc_skip_branch {
+    const char* branch;          /* the contiguous run of records whose names start with this prefix ... */
+    const char* anchor;          /* ... is issued behind the last record in front of it whose name starts with this one ... */
+    int32_t lane;                /* ... on this launch lane, 1 .. SBC_MAX_LANES-1 (a branch no record matches is skipped) */
+} sbc_skip_branch;
+typedef struct sbc_score_wiring_desc {
+    int32_t ngf, channels, nt, nr;
+    int32_t flags;               /* SBC_SCORE_* | SBC_WIRING_* */
+    const int32_t* pair_shapes;  /* SBC_SCORE_FUSE_PAIRS: n_pair_shapes x (channels, width) of the RCU blocks that become SBC_OP_CONV_PAIR records;
+                                    NULL: (32, 16), or with SBC_WIRING_PAIRS_F16W the list sbc_score_create uses in conv_mode 2 */
+    int32_t n_pair_shapes;
+    const sbc_skip_branch* skip; /* SBC_SCORE_SKIP_LANES: n_skip branches, hoisted in this order; NULL: the decoder's five skip branches on lane 1 */
+    int32_t n_skip;
+} sbc_score_wiring_desc;
+#define SBC_WIRING_OVERLAP       0x100 /* independent branches below full resolution as SBC_OP_SIDE records, joined by an SBC_OP_JOIN record */
+#define SBC_WIRING_PRIVATE_SLOTS 0x200 /* every tensor in a buffer of its own (training reads every activation again on the way back) */
+#define SBC_WIRING_PAIRS_F16W    0x400 /* pair_shapes = NULL stands for the fp16-weight mode's longer list */
+typedef struct sbc_wiring_tensor { const char* name; int32_t h, w, c, slot; } sbc_wiring_tensor;     /* per sample, NHWC; slot: index into slot_elems
+                                                                                                        (-1: named by no record -- a merged SBC_OP_CHAIN keeps it on chip) */
+typedef struct sbc_wiring_block {                  /* one block of an SBC_OP_CHAIN record: state_dict keys, NULL = none */
+    int32_t type, dil;                             /* SBC_CHAIN_*; dil: RES blocks */
+    const char *w1, *w2, *bias1, *bias2, *norm1, *norm2, *w3, *bias3;      /* bias1 .. bias3: RES blocks only (w3 / bias3: its shortcut convolution) */
+} sbc_wiring_block;
+typedef struct sbc_wiring_record {
+    int32_t kind, flags, ksize, dil, tag;          /* as in sbc_op (flags without SBC_OP_SIDE / SBC_OP_JOIN and without a conv_mode's SBC_CONV_* bits) */
+    int32_t src, dst, stats, res1, res2, up;       /* indices into tensors, -1 = none */
+    int32_t moments;                               /* second output: tile moments of dst (SBC_EPI_MOMENTS_OUT) */
+    int32_t geom;                                  /* SBC_OP_INORM_STATS from tile moments: the tensor whose (H, W, C) the launch describes */
+    int32_t side, join;                            /* SBC_WIRING_OVERLAP: the record takes SBC_OP_SIDE / SBC_OP_JOIN */
+    int32_t lane, signal, wait[2];                 /* as in sbc_op */
+    int32_t first_block, n_blocks;                 /* SBC_OP_CHAIN: blocks[first_block .. first_block + n_blocks) */
+    const char* name;                              /* of the layer the record computes (skip branches and anchors are named by prefixes of it) */
+    const char *weight, *bias, *weight2, *bias2;   /* state_dict keys, NULL = none; SBC_OP_INORM_STATS: weight = the norm's prefix */
+    const char *norm2;                             /* SBC_OP_RES_BLOCK: the second norm's prefix */
+    const char *norm_key;                          /* SBC_PRO_NORM_SELF: the prefix of the norm whose (alpha | gamma | beta) sbc_op.stats points at */
+} sbc_wiring_record;
+typedef struct sbc_score_wiring_view {
+    const sbc_wiring_tensor* tensors;
+    const sbc_wiring_record* records;
+    const sbc_wiring_block* blocks;
+    const int64_t* slot_elems;                     /* per-sample float32 elements of each buffer */
+    int32_t n_tensors, n_records, n_blocks, n_slots;
+    int32_t x, out;                                /* the network's input and output tensors, [nt][nr][channels] */
+} sbc_score_wiring_view;
+typedef struct sbc_score_wiring sbc_score_wiring;
+int sbc_score_wiring_create(const sbc_score_wiring_desc* desc, sbc_score_wiring** out);
+int sbc_score_wiring_read(const sbc_score_wiring* wiring, sbc_score_wiring_view* view);
+void sbc_score_wiring_destroy(sbc_score_wiring* wiring);
 
 /* fp16 weight forms for SBC_CONV_F16W (round to nearest even): the layouts of sbc_pack_conv_weight_split /
  * sbc_pack_conv_weight_winograd_split with a single fp16 term, [k*k | 16][cin/16][cout/32][64 lanes][8] uint16.  The

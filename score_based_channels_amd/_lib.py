@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SBC_LIB_PATH') or os.path.join(_HERE, 'libsbc_hip.so')   # env override: A/B builds (tools/)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 EXPORTS = ('sbc_abi_version', 'sbc_set_persistent_cus', 'sbc_last_error', 'sbc_device_count', 'sbc_op_launch', 'sbc_plan_create',
            'sbc_plan_run', 'sbc_plan_set_persistent_cus', 'sbc_plan_destroy', 'sbc_plan_profile', 'sbc_plan_profile_read',
@@ -18,7 +18,7 @@ EXPORTS = ('sbc_abi_version', 'sbc_set_persistent_cus', 'sbc_last_error', 'sbc_d
            'sbc_pack_conv_weight_f16x2', 'sbc_pack_conv_weight_winograd_f16x2', 'sbc_pack_conv_weight_pooled_f16x2', 'sbc_range_flag',
            'sbc_f16x2_calibration_input', 'sbc_f16x2_calibrate', 'sbc_debug_philox4x32', 'sbc_debug_complex_normal',
            'sbc_score_create', 'sbc_score_buffers', 'sbc_score_ops', 'sbc_score_level_source', 'sbc_score_forward',
-           'sbc_score_destroy', 'sbc_wgrad_scratch_floats', 'sbc_l1_lifted_run', 'sbc_ls_regularized',
+           'sbc_score_destroy', 'sbc_score_wiring_create', 'sbc_score_wiring_read', 'sbc_score_wiring_destroy', 'sbc_wgrad_scratch_floats', 'sbc_l1_lifted_run', 'sbc_ls_regularized',
            'sbc_ldamp_create', 'sbc_ldamp_destroy', 'sbc_ldamp_workspace_floats', 'sbc_ldamp_denoise', 'sbc_ldamp_run', 'sbc_ldamp_stage',
            'sbc_debug_ldamp_directions',
            'sbc_wgan_create', 'sbc_wgan_destroy', 'sbc_wgan_workspace_floats', 'sbc_wgan_generate', 'sbc_wgan_run', 'sbc_wgan_stage',
@@ -87,6 +87,36 @@ class sbc_tensor_ref(C.Structure):
 class sbc_score_desc(C.Structure):
     _fields_ = [('ngf', C.c_int32), ('channels', C.c_int32), ('nt', C.c_int32), ('nr', C.c_int32), ('batch', C.c_int32),
                 ('conv_mode', C.c_int32), ('sigmas', C.c_void_p), ('num_classes', C.c_int32), ('flags', C.c_int32)]
+
+
+# the wiring of the score network (plan.py reads it; ABI 15)
+class sbc_skip_branch(C.Structure):
+    _fields_ = [('branch', C.c_char_p), ('anchor', C.c_char_p), ('lane', C.c_int32)]
+
+
+class sbc_score_wiring_desc(C.Structure):
+    _fields_ = [('ngf', C.c_int32), ('channels', C.c_int32), ('nt', C.c_int32), ('nr', C.c_int32), ('flags', C.c_int32),
+                ('pair_shapes', C.POINTER(C.c_int32)), ('n_pair_shapes', C.c_int32), ('skip', C.POINTER(sbc_skip_branch)), ('n_skip', C.c_int32)]
+
+
+class sbc_wiring_tensor(C.Structure):
+    _fields_ = [('name', C.c_char_p), ('h', C.c_int32), ('w', C.c_int32), ('c', C.c_int32), ('slot', C.c_int32)]
+
+
+class sbc_wiring_block(C.Structure):
+    _fields_ = [('type', C.c_int32), ('dil', C.c_int32)] + [(k, C.c_char_p) for k in ('w1', 'w2', 'bias1', 'bias2', 'norm1', 'norm2', 'w3', 'bias3')]
+
+
+class sbc_wiring_record(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ('kind', 'flags', 'ksize', 'dil', 'tag', 'src', 'dst', 'stats', 'res1', 'res2', 'up', 'moments', 'geom',
+                                         'side', 'join', 'lane', 'signal')] + \
+               [('wait', C.c_int32 * 2), ('first_block', C.c_int32), ('n_blocks', C.c_int32)] + \
+               [(k, C.c_char_p) for k in ('name', 'weight', 'bias', 'weight2', 'bias2', 'norm2', 'norm_key')]
+
+
+class sbc_score_wiring_view(C.Structure):
+    _fields_ = [('tensors', C.POINTER(sbc_wiring_tensor)), ('records', C.POINTER(sbc_wiring_record)), ('blocks', C.POINTER(sbc_wiring_block)),
+                ('slot_elems', C.POINTER(C.c_int64))] + [(k, C.c_int32) for k in ('n_tensors', 'n_records', 'n_blocks', 'n_slots', 'x', 'out')]
 
 
 # classical baselines (baselines.py): lifted-DFT l1 (Lasso / fsAD) and regularised least squares (ML)
@@ -169,6 +199,10 @@ def lib():
     h.sbc_score_forward.argtypes = [C.c_void_p, C.c_void_p]
     h.sbc_score_destroy.argtypes = [C.c_void_p]
     h.sbc_score_destroy.restype = None
+    h.sbc_score_wiring_create.argtypes = [C.POINTER(sbc_score_wiring_desc), C.POINTER(C.c_void_p)]
+    h.sbc_score_wiring_read.argtypes = [C.c_void_p, C.POINTER(sbc_score_wiring_view)]
+    h.sbc_score_wiring_destroy.argtypes = [C.c_void_p]
+    h.sbc_score_wiring_destroy.restype = None
     h.sbc_wgrad_scratch_floats.argtypes = [C.c_int32] * 6
     h.sbc_wgrad_scratch_floats.restype = C.c_int64
     h.sbc_l1_lifted_run.argtypes = [C.POINTER(sbc_l1_lifted_desc), C.c_void_p]

@@ -58,7 +58,7 @@ def shared_init(n_channels, nt, nr, seed, combo):
 def batch_limit(net, nt, nr, requested, reserve=0.25):
     """Largest lock-step batch for an ``nt x nr`` array: bounded by the caller's ``requested`` size, by the 32-bit element
     index of the convolution kernels (``B * Nt * Nr * ngf`` elements in the largest tensor) and by the free device memory
-    (the activation slots of ``plan.assign_slots`` dominate: ~1 MB per trajectory at 64x16, 16 MB at 256x64), keeping
+    (the activation slots of the plan (``ScorePlan.slot_elems``) dominate: ~1 MB per trajectory at 64x16, 16 MB at 256x64), keeping
     ``reserve`` of it for the rest of the process.  In ``conv_mode f16x2`` a flagged chunk is re-run with the UNFUSED ``bf16x3``
     plan (``net.fallback_plan_slot_elems``: ~15 % more slot memory at 64x16): the chunk is sized for the larger of the two, so the
     re-run cannot run out of memory exactly when it is needed."""

@@ -52,7 +52,7 @@ DEFAULT_FUSE_DOWN = True
 # the normalizer's statistics inside the end-convolution launch (SBC_PRO_NORM_SELF on the END_CONV record; csrc/ops.hip: end_conv_self_kernel)
 DEFAULT_FUSE_END = True
 # Small batches (a rank's share when a test_score run is sharded over several GPUs): the decoder's skip branches on launch lanes of
-# their own beside the latency-bound low-resolution launches (plan.hoist_skip_branches; identical results).  Batches of at most this
+# their own beside the latency-bound low-resolution launches (csrc/score_wire.cpp: hoist_skip_branches; identical results).  Batches of at most this
 # many 64 x 16-equivalent trajectories (B Nt Nr / 1024) take that plan
 # (ScoreNet(skip_overlap=False) turns it off).
 SKIP_OVERLAP_MAX_T = 600
@@ -108,7 +108,7 @@ class ScoreNet:
         # fuse_end: the normalizer's statistics inside the end-convolution launch (fp32 vector arithmetic in every conv_mode; part of the
         # fused default plan, so tied to fuse_pairs like the others: the unfused plan stays what the bf16x3 re-run of a flagged batch uses)
         self.fuse_end = (DEFAULT_FUSE_END and self.fuse_pairs) if fuse_end is None else bool(fuse_end)
-        # skip_overlap: True (default; plan.DEFAULT_SKIP_SPEC), False, or a spec of plan.hoist_skip_branches -- applied to small batches only
+        # skip_overlap: True (default; plan.DEFAULT_SKIP_SPEC), False, or a spec like it (plan.build_score_plan) -- applied to small batches only
         self.skip_overlap = True if skip_overlap is None else skip_overlap
         self.config = config
         m, d = config.model, config.data

@@ -1,6 +1,8 @@
 """The self-sufficient C boundary (``sbc_score_*``, include/sbc_hip.h): a host that is not Python gets the whole score
-network from the checkpoint tensors in one call.  Held to the Python host (plan.py / scorenet.py): identical operator
-records, bit-identical outputs, and a full Langevin-step plan composed from ``sbc_score_ops``.  ``pytest -m gpu``."""
+network from the checkpoint tensors in one call.  Both hosts take their records from the library's one wiring (csrc/score_wire.cpp;
+tests/test_plan_golden_cpu.py holds it); what is held to the Python host (scorenet.py) here is the rest of ``sbc_score_create`` -- the
+gates it puts in front of the wiring, weight packing, record binding, calibration: identical operator records, bit-identical outputs,
+and a full Langevin-step plan composed from ``sbc_score_ops``.  ``pytest -m gpu``."""
 import ctypes as C
 
 import numpy as np
@@ -36,7 +38,7 @@ def test_c_built_score_network_equals_python_host(weights64, mode):
     B, nt, nr = 3, 64, 16
     mode, *opts = mode.split('+')
     pairs, fold, res, chain, down, end = 'pairs' in opts, 'fold' in opts, 'res' in opts, 'chain' in opts, 'down' in opts, 'end' in opts
-    lanes = 'lanes' in opts                 # SBC_SCORE_SKIP_LANES: the skip branches on launch lane 1 (plan.hoist_skip_branches)
+    lanes = 'lanes' in opts                 # SBC_SCORE_SKIP_LANES: the skip branches on launch lane 1
     h = _create(sd, cfg, B, nt, nr, mode, pairs, fold, res, chain, down, end, lanes)
     try:
         ops_p, n = C.POINTER(_lib.sbc_op)(), C.c_int32()

@@ -759,7 +759,7 @@ def test_overlapped_branches_do_not_change_results(weights64):
 
 def test_skip_overlap_plan_equals_sequential_plan(weights64):
     """Round 6: batches of at most scorenet.SKIP_OVERLAP_MAX_T trajectories run the decoder's skip branches (refineK.adapt_convs.0) on
-    launch lanes of their own (sbc_op.lane / signal / wait, plan.hoist_skip_branches) beside the latency-bound low-resolution launches.
+    launch lanes of their own (sbc_op.lane / signal / wait, plan.build_score_plan(skip_overlap=...)) beside the latency-bound low-resolution launches.
     Same records, same arguments, other order and streams: bit-identical to the sequential plan -- module call, eager Langevin steps and
     hipGraph replay (a captured graph is flat: the lane records in list order on the run stream, csrc/api.hip) -- also when two sub-batches
     with lanes share the chip, and repeatedly (a race would show as a flicker)."""

@@ -133,7 +133,7 @@ def test_chain_plan_matches_reference_forward(weights64):
     low, mid, top = [op for op in chains if op.src.h == 8], [op for op in chains if op.src.h == 16], [op for op in chains if op.src.h == 32]
     assert len(base.ops) == 125 and len(pl.ops) == 57 and len(low) == 8 and len(mid) == 3 and len(top) == 2
     # 32 x 8: refine4's adapt convolutions at 64 channels; its CRP + output RCU + refine5's second adapt pair at 32 (res2.1 stays on
-    # its own launches: plan.chain_fusable)
+    # its own launches: csrc/score_wire.cpp: chain_fusable)
     assert [(op.src.c, [b[0] for b in op.blocks]) for op in top] == [(64, [P.CHAIN_RCU] * 2), (32, [P.CHAIN_CRP] + [P.CHAIN_RCU] * 3)]
     assert [len(op.blocks) for op in low] == [1, 1, 6, 2, 2, 4, 2, 4] and [op.src.c for op in low] == [64, 128, 128, 128, 128, 64, 64, 64]
     assert [[b[0] for b in op.blocks] for op in low[:3]] == [[P.CHAIN_RES], [P.CHAIN_RES], [P.CHAIN_RES, P.CHAIN_RES, P.CHAIN_RCU, P.CHAIN_RCU, P.CHAIN_CRP, P.CHAIN_RCU]]
@@ -196,7 +196,7 @@ def test_conv_down_plan_matches_reference_forward(weights64):
 
 
 def test_skip_branches_on_lanes_keep_the_dataflow_and_never_share_live_storage():
-    """plan.hoist_skip_branches (round 6): the decoder's skip branches move behind their anchors onto launch lanes.  The list stays a
+    """build_score_plan(skip_overlap=True) (round 6; csrc/score_wire.cpp: hoist_skip_branches): the decoder's skip branches move behind their anchors onto launch lanes.  The list stays a
     valid sequential order (every input is produced earlier), every wait names an event an EARLIER record signals, and no record
     writes a slot that a concurrently running lane still reads or writes: for a lane record issued at i and joined at j, its input and
     output slots are touched by no other record in (i, j)."""
