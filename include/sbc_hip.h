@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SBC_ABI_VERSION 15
+#define SBC_ABI_VERSION 16
 
 typedef enum sbc_status {
     SBC_OK = 0,
@@ -437,7 +437,8 @@ int sbc_pack_conv_weight_winograd_split(const float* src, int32_t cout, int32_t 
 
 /* --- the whole score network behind one call (hosts that are not Python) -------------------------------
  * NCSNv2Deepest.forward (ncsnv2/models/ncsnv2.py:269-300) becomes ~150 sbc_op records: the library wires them and shares
- * activation storage between them (sbc_score_wiring_* below), a host packs the weights and binds device memory (the Python host:
+ * activation storage between them and turns them into sbc_op records over a host's memory (sbc_score_wiring_* below: one wiring, one
+ * binder); a host packs the weights, allocates device memory and says where each packed form lives (the Python host:
  * score_based_channels_amd/scorenet.py).  sbc_score_create does all of that inside the library from the tensors of the reference checkpoint's
  * `model_state` (names as in NCSNv2Deepest.state_dict(): "res2.0.conv2.conv.weight", "normalizer.alpha", ...; HOST
  * pointers, float32, torch layouts).  The handle owns its device memory (weights, activation slots for `batch` samples,
@@ -485,16 +486,20 @@ int sbc_score_level_source(sbc_score* score, const float* sigma_of_step, const i
 int sbc_score_forward(sbc_score* score, void* stream);
 void sbc_score_destroy(sbc_score* score);
 
-/* --- the wiring of the score network, without a device (ABI 15) --------------------------------------------------
- * Which records one score evaluation consists of, in which order and on which launch lane, and which logical tensors share a buffer:
- * what sbc_score_create binds to device memory, for hosts that bind it themselves (score_based_channels_amd/plan.py reads it into
- * its dataclasses).  Pure host code: none of the three calls initialises HIP.
- *   sbc_score_wiring_create   wires what `desc` asks for -- unlike sbc_score_create it does not look at a conv_mode and does not drop
- *                             SBC_SCORE_FOLD_STATS for arrays that are no powers of two; refusals (SBC_ERR_INVALID, sbc_last_error):
+/* --- the wiring of the score network and its binding to a host's memory, without a device (ABI 15, 16) ----------------
+ * Which records one score evaluation consists of, in which order and on which launch lane, which logical tensors share a buffer, and
+ * which packed form of which parameter each sbc_op field points at: what sbc_score_create runs, for hosts that own their device memory
+ * (score_based_channels_amd/plan.py reads the wiring into its dataclasses, scorenet.py binds it).  Pure host code: none of the calls
+ * initialises HIP or dereferences a pointer it binds.
+ *   sbc_score_wiring_create   wires what `desc` asks for; with desc.conv_mode 0 .. 3 it first applies that mode's gates (below), with -1
+ *                             none.  Refusals (SBC_ERR_INVALID, sbc_last_error):
  *                             Nt or Nr no multiple of 8, SBC_SCORE_SKIP_LANES with SBC_WIRING_OVERLAP, a skip branch that is not one
  *                             contiguous run of records or reads what its anchor does not have yet, a missing anchor, a lane outside
  *                             1 .. SBC_MAX_LANES-1, a third wait on one record, more than SBC_MAX_EVENTS events;
- *   sbc_score_wiring_read     flat arrays owned by the handle (strings included), valid until sbc_score_wiring_destroy. */
+ *   sbc_score_wiring_read     flat arrays owned by the handle (strings included), valid until sbc_score_wiring_destroy;
+ *   sbc_score_wiring_bind     (ABI 16) the wiring's records as sbc_op records over the caller's buffers -- the one place that knows which
+ *                             form goes into which field, which SBC_CONV_* / SBC_PRO_ELU_ACC bits a conv_mode adds and how an sbc_chain
+ *                             is filled. */
 typedef struct sbc_skip_branch {
     const char* branch;          /* the contiguous run of records whose names start with this prefix ... */
     const char* anchor;          /* ... is issued behind the last record in front of it whose name starts with this one ... */
@@ -504,14 +509,17 @@ typedef struct sbc_score_wiring_desc {
     int32_t ngf, channels, nt, nr;
     int32_t flags;               /* SBC_SCORE_* | SBC_WIRING_* */
     const int32_t* pair_shapes;  /* SBC_SCORE_FUSE_PAIRS: n_pair_shapes x (channels, width) of the RCU blocks that become SBC_OP_CONV_PAIR records;
-                                    NULL: (32, 16), or with SBC_WIRING_PAIRS_F16W the list sbc_score_create uses in conv_mode 2 */
+                                    NULL: (32, 16), or with conv_mode 2 that mode's longer list */
     int32_t n_pair_shapes;
     const sbc_skip_branch* skip; /* SBC_SCORE_SKIP_LANES: n_skip branches, hoisted in this order; NULL: the decoder's five skip branches on lane 1 */
     int32_t n_skip;
+    int32_t conv_mode;           /* (ABI 16) -1: wire exactly what `flags` asks for.  0 bf16x3, 1 f32, 2 f16w, 3 f16x2: the records are for that
+                                    multiplier -- SBC_SCORE_FOLD_STATS is dropped in mode 1 and for Nt or Nr that are no powers of two (the tile
+                                    moments are written by the Winograd split kernels, which take power-of-two images), and mode 2 has its
+                                    own default pair_shapes.  Which SBC_SCORE_FUSE_* a mode can run at all stays the host's business */
 } sbc_score_wiring_desc;
 #define SBC_WIRING_OVERLAP       0x100 /* independent branches below full resolution as SBC_OP_SIDE records, joined by an SBC_OP_JOIN record */
 #define SBC_WIRING_PRIVATE_SLOTS 0x200 /* every tensor in a buffer of its own (training reads every activation again on the way back) */
-#define SBC_WIRING_PAIRS_F16W    0x400 /* pair_shapes = NULL stands for the fp16-weight mode's longer list */
 typedef struct sbc_wiring_tensor { const char* name; int32_t h, w, c, slot; } sbc_wiring_tensor;     /* per sample, NHWC; slot: index into slot_elems
                                                                                                         (-1: named by no record -- a merged SBC_OP_CHAIN keeps it on chip) */
 typedef struct sbc_wiring_block {                  /* one block of an SBC_OP_CHAIN record: state_dict keys, NULL = none */
@@ -538,11 +546,32 @@ typedef struct sbc_score_wiring_view {
     const int64_t* slot_elems;                     /* per-sample float32 elements of each buffer */
     int32_t n_tensors, n_records, n_blocks, n_slots;
     int32_t x, out;                                /* the network's input and output tensors, [nt][nr][channels] */
+    int32_t n_chains;                              /* (ABI 16) the SBC_OP_CHAIN records among `records`: the sbc_chain structs a binding needs */
 } sbc_score_wiring_view;
 typedef struct sbc_score_wiring sbc_score_wiring;
 int sbc_score_wiring_create(const sbc_score_wiring_desc* desc, sbc_score_wiring** out);
 int sbc_score_wiring_read(const sbc_score_wiring* wiring, sbc_score_wiring_view* view);
 void sbc_score_wiring_destroy(sbc_score_wiring* wiring);
+/* Binding.  `params` says what the host packed and where it lives, by name: "<state_dict key>" (fp32: biases, the begin / end
+ * convolutions, and in conv_mode 1 sbc_pack_conv_weight), "<key>#winograd" (mode 1), "<key>#split" (the mode's direct form),
+ * "<key>#winograd_split" (its Winograd form), "<key>#pool" (sbc_pack_conv_weight_pooled_f16x2), and a norm's prefix for its
+ * alpha | gamma | beta [3][C].  A form that a record's kernel reads and `params` lacks is refused (SBC_ERR_INVALID; the message names
+ * the record and the form).  The forms that ride along only for sbc_f16x2_calibrate (see sbc_op.weight2_wino_split) -- the Winograd
+ * forms of CONV_PAIR / CONV_POOL / RES_BLOCK layers and of the undilated layers of a CHAIN, and in `weight`, `weight_wino_split`,
+ * `weight_wino` of a CONV_DOWN record the "#split" and "#winograd_split" forms of its first and the "#split" form of its second layer --
+ * are bound in conv_mode 3 where `params` has them and are NULL otherwise: a host that shares one weight buffer between array sizes
+ * packs them, a host with one size does not need to.  ops [n_records] and chains [n_chains] are the caller's; a CHAIN record's ext
+ * points into `chains`, the END_CONV record's at `endconv`. */
+typedef struct sbc_named_ptr { const char* name; const void* ptr; } sbc_named_ptr;
+typedef struct sbc_score_bind_desc {
+    int32_t batch, conv_mode;    /* sbc_op.B; 0 bf16x3, 1 f32, 2 f16w, 3 f16x2 */
+    void* const* slots;          /* one device buffer per slot of the wiring, [batch * slot_elems[i]] floats */
+    int32_t n_slots;
+    const sbc_named_ptr* params;
+    int32_t n_params;
+    const sbc_endconv* endconv;  /* caller-owned, read at sbc_plan_create / sbc_op_launch like every ext */
+} sbc_score_bind_desc;
+int sbc_score_wiring_bind(const sbc_score_wiring* wiring, const sbc_score_bind_desc* desc, sbc_op* ops, sbc_chain* chains);
 
 /* fp16 weight forms for SBC_CONV_F16W (round to nearest even): the layouts of sbc_pack_conv_weight_split /
  * sbc_pack_conv_weight_winograd_split with a single fp16 term, [k*k | 16][cin/16][cout/32][64 lanes][8] uint16.  The

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SBC_LIB_PATH') or os.path.join(_HERE, 'libsbc_hip.so')   # env override: A/B builds (tools/)
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 EXPORTS = ('sbc_abi_version', 'sbc_set_persistent_cus', 'sbc_last_error', 'sbc_device_count', 'sbc_op_launch', 'sbc_plan_create',
            'sbc_plan_run', 'sbc_plan_set_persistent_cus', 'sbc_plan_destroy', 'sbc_plan_profile', 'sbc_plan_profile_read',
@@ -18,7 +18,7 @@ EXPORTS = ('sbc_abi_version', 'sbc_set_persistent_cus', 'sbc_last_error', 'sbc_d
            'sbc_pack_conv_weight_f16x2', 'sbc_pack_conv_weight_winograd_f16x2', 'sbc_pack_conv_weight_pooled_f16x2', 'sbc_range_flag',
            'sbc_f16x2_calibration_input', 'sbc_f16x2_calibrate', 'sbc_debug_philox4x32', 'sbc_debug_complex_normal',
            'sbc_score_create', 'sbc_score_buffers', 'sbc_score_ops', 'sbc_score_level_source', 'sbc_score_forward',
-           'sbc_score_destroy', 'sbc_score_wiring_create', 'sbc_score_wiring_read', 'sbc_score_wiring_destroy', 'sbc_wgrad_scratch_floats', 'sbc_l1_lifted_run', 'sbc_ls_regularized',
+           'sbc_score_destroy', 'sbc_score_wiring_create', 'sbc_score_wiring_read', 'sbc_score_wiring_destroy', 'sbc_score_wiring_bind', 'sbc_wgrad_scratch_floats', 'sbc_l1_lifted_run', 'sbc_ls_regularized',
            'sbc_ldamp_create', 'sbc_ldamp_destroy', 'sbc_ldamp_workspace_floats', 'sbc_ldamp_denoise', 'sbc_ldamp_run', 'sbc_ldamp_stage',
            'sbc_debug_ldamp_directions',
            'sbc_wgan_create', 'sbc_wgan_destroy', 'sbc_wgan_workspace_floats', 'sbc_wgan_generate', 'sbc_wgan_run', 'sbc_wgan_stage',
@@ -96,7 +96,8 @@ class sbc_skip_branch(C.Structure):
 
 class sbc_score_wiring_desc(C.Structure):
     _fields_ = [('ngf', C.c_int32), ('channels', C.c_int32), ('nt', C.c_int32), ('nr', C.c_int32), ('flags', C.c_int32),
-                ('pair_shapes', C.POINTER(C.c_int32)), ('n_pair_shapes', C.c_int32), ('skip', C.POINTER(sbc_skip_branch)), ('n_skip', C.c_int32)]
+                ('pair_shapes', C.POINTER(C.c_int32)), ('n_pair_shapes', C.c_int32), ('skip', C.POINTER(sbc_skip_branch)), ('n_skip', C.c_int32),
+                ('conv_mode', C.c_int32)]             # ABI 16: -1 = no gates, or CONV_MODE_IDS[...]
 
 
 class sbc_wiring_tensor(C.Structure):
@@ -116,7 +117,20 @@ class sbc_wiring_record(C.Structure):
 
 class sbc_score_wiring_view(C.Structure):
     _fields_ = [('tensors', C.POINTER(sbc_wiring_tensor)), ('records', C.POINTER(sbc_wiring_record)), ('blocks', C.POINTER(sbc_wiring_block)),
-                ('slot_elems', C.POINTER(C.c_int64))] + [(k, C.c_int32) for k in ('n_tensors', 'n_records', 'n_blocks', 'n_slots', 'x', 'out')]
+                ('slot_elems', C.POINTER(C.c_int64))] + [(k, C.c_int32) for k in ('n_tensors', 'n_records', 'n_blocks', 'n_slots', 'x', 'out', 'n_chains')]
+
+
+# sbc_score_wiring_bind (scorenet.py; ABI 16)
+CONV_MODE_IDS = {'bf16x3': 0, 'f32': 1, 'f16w': 2, 'f16x2': 3}      # sbc_score_desc / sbc_score_wiring_desc / sbc_score_bind_desc .conv_mode
+
+
+class sbc_named_ptr(C.Structure):
+    _fields_ = [('name', C.c_char_p), ('ptr', C.c_void_p)]
+
+
+class sbc_score_bind_desc(C.Structure):
+    _fields_ = [('batch', C.c_int32), ('conv_mode', C.c_int32), ('slots', C.POINTER(C.c_void_p)), ('n_slots', C.c_int32),
+                ('params', C.POINTER(sbc_named_ptr)), ('n_params', C.c_int32), ('endconv', C.POINTER(sbc_endconv))]
 
 
 # classical baselines (baselines.py): lifted-DFT l1 (Lasso / fsAD) and regularised least squares (ML)
@@ -203,6 +217,7 @@ def lib():
     h.sbc_score_wiring_read.argtypes = [C.c_void_p, C.POINTER(sbc_score_wiring_view)]
     h.sbc_score_wiring_destroy.argtypes = [C.c_void_p]
     h.sbc_score_wiring_destroy.restype = None
+    h.sbc_score_wiring_bind.argtypes = [C.c_void_p, C.POINTER(sbc_score_bind_desc), C.POINTER(sbc_op), C.POINTER(sbc_chain)]
     h.sbc_wgrad_scratch_floats.argtypes = [C.c_int32] * 6
     h.sbc_wgrad_scratch_floats.restype = C.c_int64
     h.sbc_l1_lifted_run.argtypes = [C.POINTER(sbc_l1_lifted_desc), C.c_void_p]

@@ -1,12 +1,15 @@
 // sbc_score_*: the whole NCSNv2Deepest score network behind ONE C call, for hosts that are not Python.
 //
-// score_wire.cpp wires ncsnv2/models/ncsnv2.py:269-300 into ~150 fused operator records and shares activation storage between
-// tensors with disjoint lifetimes -- for this file and, through sbc_score_wiring_*, for the product's Python host (plan.py /
-// scorenet.py).  This file re-orders the weights and binds everything to device memory, so that a C / C++ / Go / Rust host gets a
+// score_wire.cpp wires ncsnv2/models/ncsnv2.py:269-300 into ~150 fused operator records, shares activation storage between
+// tensors with disjoint lifetimes and binds the records to a host's memory -- for this file and, through sbc_score_wiring_*, for the
+// product's Python host (plan.py / scorenet.py).  This file packs the forms of the weights its one array size runs, allocates device
+// memory and hands both to that binder, so that a C / C++ / Go / Rust host gets a
 // score evaluation from (state_dict tensors, batch size): sbc_score_create -> sbc_score_buffers -> sbc_score_forward, or
 // sbc_score_ops to extend the record list with SBC_OP_LANGEVIN / SBC_OP_STEP_INC into a full annealed-Langevin step plan
-// (sbc_plan_create).  tests/test_gpu_capi.py holds packing and binding to the Python host: identical records, bit-identical outputs.
+// (sbc_plan_create).  tests/test_gpu_capi.py holds packing and the choice of forms to the Python host: identical records,
+// bit-identical outputs.
 #include <string.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 #include "common.h"
@@ -33,17 +36,14 @@ namespace {
 
 // ---- the steps of sbc_score_create behind the wiring, in the order they run -----------------------------------------------------
 
-// 1. the wiring this handle's conv_mode and array size allow (the gates scorenet.ScoreNet.score_plan applies for the Python host)
+// 1. the wiring of this handle's flags behind the gates of its conv_mode and array size
 int wire(sbc_score& s) {
     const sbc_score_desc& d = s.desc;
     sbc_score_wiring_desc wd;
     memset(&wd, 0, sizeof(wd));
-    wd.ngf = d.ngf; wd.channels = d.channels; wd.nt = d.nt; wd.nr = d.nr;
+    wd.ngf = d.ngf; wd.channels = d.channels; wd.nt = d.nt; wd.nr = d.nr; wd.conv_mode = d.conv_mode;
     wd.flags = d.flags & (SBC_SCORE_FOLD_STATS | SBC_SCORE_FUSE_PAIRS | SBC_SCORE_FUSE_RES | SBC_SCORE_FUSE_CHAIN | SBC_SCORE_FUSE_DOWN |
                           SBC_SCORE_FUSE_END | SBC_SCORE_SKIP_LANES);
-    // tile moments: not in the fp32 mode, and conv_wx3 takes power-of-two images
-    if (d.conv_mode == 1 || (d.nt & (d.nt - 1)) || (d.nr & (d.nr - 1))) wd.flags &= ~SBC_SCORE_FOLD_STATS;
-    if (d.conv_mode == 2) wd.flags |= SBC_WIRING_PAIRS_F16W;
     const int rc = sbc::wire::build(wd, s.w);
     if (rc) sbc::set_error("sbc_score_create: %s", std::string(sbc_last_error()).c_str());
     return rc;
@@ -155,84 +155,19 @@ int allocate(sbc_score& s) {
     return SBC_OK;
 }
 
-// 4. records (scorenet.ScoreNet.bind) and the plan that runs them
+// 4. records: the one binder (score_wire.cpp) over this handle's slots and whatever pack_params put into the image; and the plan
+// that runs them
 int bind_records(sbc_score& s) {
-    const int conv_mode = s.desc.conv_mode;
-    const bool f16w = conv_mode == 2, f16x2 = conv_mode == 3;
-    size_t n_chains = 0;
-    for (const POp& o : s.w.records) n_chains += o.kind == SBC_OP_CHAIN;
-    s.chains.reserve(n_chains);
-    auto wp = [&](const std::string& key) -> const void* { return s.params.dev_at(key); };
-    for (const POp& o : s.w.records) {
-        sbc_op r;
-        memset(&r, 0, sizeof(r));
-        const Tn& src = s.w.tensors[o.geom >= 0 ? o.geom : o.src];     // (statistics from tile moments: the image's dims)
-        const Tn& dst = s.w.tensors[o.dst];
-        r.kind = o.kind; r.flags = o.flags; r.B = s.desc.batch; r.H = src.h; r.W = src.w;
-        r.cin = src.c; r.cout = dst.c; r.ksize = o.ksize; r.dil = o.dil; r.tag = o.tag;
-        r.lane = o.lane; r.signal = o.signal; r.wait[0] = o.wait0; r.wait[1] = o.wait1;
-        r.in = s.slots[s.w.tensors[o.src].slot]; r.out = s.slots[dst.slot];
-        if (o.moments >= 0) r.aux = s.slots[s.w.tensors[o.moments].slot];
-        if (o.kind == SBC_OP_CONV_PAIR) {
-            r.weight_split = wp(o.weight + "#split");
-            r.weight2_split = wp(o.weight2 + "#split");
-            if (f16x2) { r.weight_wino_split = wp(o.weight + "#winograd_split"); r.weight2_wino_split = wp(o.weight2 + "#winograd_split"); }   // calibration only
-            r.flags |= f16w ? SBC_CONV_F16W : SBC_CONV_F16X2;
-        } else if (o.kind == SBC_OP_CONV_POOL) {
-            r.weight_split = wp(o.weight + "#split");
-            if (f16x2) r.weight_wino_split = wp(o.weight + "#winograd_split");
-            r.flags |= f16w ? SBC_CONV_F16W : SBC_CONV_F16X2;
-        } else if (o.kind == SBC_OP_CONV_DOWN) {
-            r.weight_split = wp(o.weight + "#pool");
-            r.weight2_split = wp(o.weight2 + "#pool");
-            r.bias2 = wp(o.bias2);
-            r.flags |= SBC_CONV_F16X2;
-        } else if (o.kind == SBC_OP_CHAIN) {
-            sbc_chain ch;
-            memset(&ch, 0, sizeof(ch));
-            ch.n_blocks = (int32_t)o.blocks.size();
-            for (size_t k = 0; k < o.blocks.size(); ++k) {
-                ch.type[k] = o.blocks[k].type;
-                const sbc::wire::Block& bl = o.blocks[k];
-                ch.w1[k] = wp(bl.w1 + "#split"); ch.w2[k] = wp(bl.w2 + "#split");
-                ch.w1_wino[k] = wp(bl.w1 + "#winograd_split"); ch.w2_wino[k] = wp(bl.w2 + "#winograd_split");
-                if (bl.type == SBC_CHAIN_RES) {
-                    ch.dil[k] = bl.dil;
-                    ch.bias1[k] = (const float*)wp(bl.bias1); ch.bias2[k] = (const float*)wp(bl.bias2);
-                    ch.norm1[k] = (const float*)wp(bl.norm1); ch.norm2[k] = (const float*)wp(bl.norm2);
-                    if (!bl.w3.empty()) { ch.w3[k] = wp(bl.w3 + "#split"); ch.bias3[k] = (const float*)wp(bl.bias3); }
-                }
-            }
-            s.chains.push_back(ch);
-            r.ext = &s.chains.back();
-            r.flags |= SBC_CONV_F16X2;
-        } else if (o.kind == SBC_OP_RES_BLOCK) {
-            r.weight_split = wp(o.weight + "#split");
-            r.weight2_split = wp(o.weight2 + "#split");
-            r.weight_wino_split = wp(o.weight + "#winograd_split"); r.weight2_wino_split = wp(o.weight2 + "#winograd_split");
-            r.bias2 = wp(o.bias2);
-            r.norm2 = wp(o.norm2);
-            r.flags |= SBC_CONV_F16X2;
-        } else if (o.kind != SBC_OP_CONV) {
-            r.weight = wp(o.weight);
-        } else if (conv_mode == 1) {
-            r.weight = wp(o.weight);
-            if (o.ksize == 3 && o.dil == 1) r.weight_wino = wp(o.weight + "#winograd");
-        } else {
-            r.weight_split = wp(o.weight + "#split");
-            if (o.ksize == 3 && o.dil == 1) r.weight_wino_split = wp(o.weight + "#winograd_split");
-            if (f16w) r.flags |= SBC_CONV_F16W;
-            if (f16x2) r.flags |= SBC_CONV_F16X2;
-        }
-        if ((conv_mode == 0 || conv_mode == 1) && o.kind == SBC_OP_CONV && (o.flags & SBC_PRO_ELU)) r.flags |= SBC_PRO_ELU_ACC;   // scorenet.bind
-        if (!o.bias.empty()) r.bias = wp(o.bias);
-        if (o.stats >= 0) r.stats = s.slots[s.w.tensors[o.stats].slot];
-        if (!o.norm_key.empty()) r.stats = wp(o.norm_key);
-        if (o.res1 >= 0) r.res1 = s.slots[s.w.tensors[o.res1].slot];
-        if (o.res2 >= 0) r.res2 = s.slots[s.w.tensors[o.res2].slot];
-        if (o.up >= 0) { r.up = s.slots[s.w.tensors[o.up].slot]; r.up_h = s.w.tensors[o.up].h; r.up_w = s.w.tensors[o.up].w; }
-        if (o.kind == SBC_OP_END_CONV) r.ext = &s.endc;
-        s.ops.push_back(r);
+    std::vector<sbc_named_ptr> params;
+    for (const auto& kv : s.params.off) params.push_back({kv.first.c_str(), s.params.dev + kv.second});
+    std::vector<void*> slots(s.slots.begin(), s.slots.end());
+    const sbc_score_bind_desc bd = {s.desc.batch, s.desc.conv_mode, slots.data(), (int32_t)slots.size(), params.data(), (int32_t)params.size(), &s.endc};
+    s.ops.resize(s.w.records.size());
+    s.chains.resize(std::count_if(s.w.records.begin(), s.w.records.end(), [](const POp& o) { return o.kind == SBC_OP_CHAIN; }));
+    const int rc = sbc::wire::bind(s.w, bd, s.ops.data(), s.chains.data());
+    if (rc) {
+        sbc::set_error("sbc_score_create: %s", std::string(sbc_last_error()).c_str());
+        return rc;
     }
     return sbc_plan_create(s.ops.data(), (int32_t)s.ops.size(), &s.plan);
 }

@@ -416,14 +416,18 @@ int build(const sbc_score_wiring_desc& d, Wiring& w) {
     const int ngf = d.ngf, nt = d.nt, nr = d.nr;
     WIRE_REQUIRE(nt > 0 && nr > 0 && nt % 8 == 0 && nr % 8 == 0, "Nt and Nr must be multiples of 8 (three 2x mean-pools), got %dx%d", nt, nr);
     WIRE_REQUIRE(ngf > 0 && d.channels > 0, "ngf and channels must be positive, got %d and %d", ngf, d.channels);
-    const bool lanes = (d.flags & SBC_SCORE_SKIP_LANES) != 0;
-    WIRE_REQUIRE(!(lanes && (d.flags & SBC_WIRING_OVERLAP)), "skip_overlap and overlap (SBC_OP_SIDE records) do not mix");
+    WIRE_REQUIRE(d.conv_mode >= -1 && d.conv_mode <= 3, "conv_mode must be -1 (none) or 0 bf16x3, 1 f32, 2 f16w, 3 f16x2, got %d", d.conv_mode);
+    int flags = d.flags;
+    // the gates of a conv_mode: the tile moments are written by the Winograd split kernels (not fp32), and conv_wx3 takes power-of-two images
+    if (d.conv_mode >= 0 && (d.conv_mode == 1 || (nt & (nt - 1)) || (nr & (nr - 1)))) flags &= ~SBC_SCORE_FOLD_STATS;
+    const bool lanes = (flags & SBC_SCORE_SKIP_LANES) != 0;
+    WIRE_REQUIRE(!(lanes && (flags & SBC_WIRING_OVERLAP)), "skip_overlap and overlap (SBC_OP_SIDE records) do not mix");
     WIRE_REQUIRE(d.n_pair_shapes >= 0 && d.n_skip >= 0, "negative count of pair shapes or skip branches");
     w = Wiring();
-    Builder b{ngf, nt, nr, d.flags, {}, w.tensors, w.records};
-    if (d.flags & SBC_SCORE_FUSE_PAIRS) {
+    Builder b{ngf, nt, nr, flags, {}, w.tensors, w.records};
+    if (flags & SBC_SCORE_FUSE_PAIRS) {
         if (d.pair_shapes) for (int i = 0; i < d.n_pair_shapes; ++i) b.pair_shapes.push_back({d.pair_shapes[2 * i], d.pair_shapes[2 * i + 1]});
-        else if (d.flags & SBC_WIRING_PAIRS_F16W) b.pair_shapes.assign(std::begin(PAIR_SHAPES_F16W), std::end(PAIR_SHAPES_F16W));
+        else if (d.conv_mode == 2) b.pair_shapes.assign(std::begin(PAIR_SHAPES_F16W), std::end(PAIR_SHAPES_F16W));
         else b.pair_shapes.assign(std::begin(PAIR_SHAPES), std::end(PAIR_SHAPES));
     }
     w.x = b.tensor("x", nt, nr, d.channels);
@@ -445,7 +449,7 @@ int build(const sbc_score_wiring_desc& d, Wiring& w) {
     const int ref4 = b.refine("refine4.", {layers[1], ref3}, ngf);
     const int ref5 = b.refine("refine5.", {layers[0], ref4}, ngf, true);
     w.out = b.tensor("score", nt, nr, d.channels);
-    const bool self = (d.flags & SBC_SCORE_FUSE_END) && end_fusable(nt, nr, ngf);
+    const bool self = (flags & SBC_SCORE_FUSE_END) && end_fusable(nt, nr, ngf);
     // (SBC_SCORE_FUSE_END: the normalizer's statistics are formed inside the end-convolution launch -- a workgroup holds whole samples,
     // the tensor is read once instead of twice, and there is no statistics record)
     const int sn = self ? -1 : b.stats("normalizer", ref5, "normalizer", false);
@@ -460,10 +464,118 @@ int build(const sbc_score_wiring_desc& d, Wiring& w) {
     }
     for (Record& o : w.records)             // (after the statistics folding, which adds SBC_EPI_MOMENTS_OUT to producers)
         if (o.tag == TAG_CONV_MID && !(o.flags & (SBC_PRO_NORM | SBC_EPI_UP | SBC_EPI_MOMENTS_OUT))) o.tag = TAG_DIRECT_MID;
-    if (d.flags & SBC_WIRING_PRIVATE_SLOTS) {
+    if (flags & SBC_WIRING_PRIVATE_SLOTS) {
         for (size_t i = 0; i < w.tensors.size(); ++i) { w.tensors[i].slot = (int)i; w.slot_elems.push_back(w.tensors[i].elems()); }
     } else {
         assign_slots(w);
+    }
+    return SBC_OK;
+}
+
+// ---- binding: the records over a host's memory (include/sbc_hip.h: sbc_score_wiring_bind) ---------------------------------------
+int bind(const Wiring& w, const sbc_score_bind_desc& d, sbc_op* ops, sbc_chain* chains) {
+    WIRE_REQUIRE(ops && d.batch > 0 && d.conv_mode >= 0 && d.conv_mode <= 3,
+                 "sbc_score_wiring_bind: ops, a positive batch and conv_mode in {0 bf16x3, 1 f32, 2 f16w, 3 f16x2} required");
+    WIRE_REQUIRE(d.slots && d.n_slots == (int)w.slot_elems.size(), "sbc_score_wiring_bind: the wiring has %d slots, got %d",
+                 (int)w.slot_elems.size(), d.n_slots);
+    WIRE_REQUIRE(d.n_params >= 0 && (d.params || !d.n_params) && d.endconv, "sbc_score_wiring_bind: params or endconv is NULL");
+    std::map<std::string, const void*> table;
+    for (int i = 0; i < d.n_params; ++i) {
+        WIRE_REQUIRE(d.params[i].name && d.params[i].ptr, "sbc_score_wiring_bind: parameter %d has no name or pointer", i);
+        table[d.params[i].name] = d.params[i].ptr;
+    }
+    const bool f32 = d.conv_mode == 1, f16w = d.conv_mode == 2, f16x2 = d.conv_mode == 3;
+    const Record* rec = nullptr;
+    const char* lacks = nullptr;             // the first form `rec` reads that the table lacks
+    auto need = [&](const std::string& key) -> const void* {      // what the record's kernel reads ("": the record has none)
+        if (key.empty()) return nullptr;
+        const auto it = table.find(key);
+        if (it != table.end()) return it->second;
+        if (!lacks) {
+            lacks = key.c_str();
+            set_error("sbc_score_wiring_bind: record '%s' reads '%s', which params lacks", rec->name.c_str(), lacks);
+        }
+        return nullptr;
+    };
+    auto calib = [&](const std::string& key) -> const void* {     // what only sbc_f16x2_calibrate writes a scale into: where the host has it
+        const auto it = f16x2 ? table.find(key) : table.end();
+        return it == table.end() ? nullptr : it->second;
+    };
+    auto slot = [&](int tensor) -> void* { return tensor < 0 ? nullptr : d.slots[w.tensors[tensor].slot]; };
+    for (const Record& o : w.records) {
+        rec = &o;
+        sbc_op& r = *ops++;
+        memset(&r, 0, sizeof(r));
+        const Tensor& src = w.tensors[o.geom >= 0 ? o.geom : o.src];     // (statistics from tile moments: the image's dims)
+        r.kind = o.kind; r.flags = o.flags | (o.side ? SBC_OP_SIDE : 0) | (o.join ? SBC_OP_JOIN : 0);
+        r.B = d.batch; r.H = src.h; r.W = src.w; r.cin = src.c; r.cout = w.tensors[o.dst].c;
+        r.ksize = o.ksize; r.dil = o.dil; r.tag = o.tag;
+        r.lane = o.lane; r.signal = o.signal; r.wait[0] = o.wait0; r.wait[1] = o.wait1;
+        r.in = slot(o.src); r.out = slot(o.dst); r.aux = slot(o.moments);
+        r.res1 = slot(o.res1); r.res2 = slot(o.res2); r.up = slot(o.up);
+        if (o.up >= 0) { r.up_h = w.tensors[o.up].h; r.up_w = w.tensors[o.up].w; }
+        r.stats = o.norm_key.empty() ? slot(o.stats) : need(o.norm_key);     // SBC_PRO_NORM_SELF: the norm's (alpha | gamma | beta)
+        r.bias = need(o.bias);
+        const bool wino = o.ksize == 3 && o.dil == 1;
+        switch (o.kind) {
+        case SBC_OP_CONV:
+            if (f32) {
+                r.weight = need(o.weight);
+                if (wino) r.weight_wino = need(o.weight + "#winograd");
+            } else {
+                r.weight_split = need(o.weight + "#split");
+                if (wino) r.weight_wino_split = need(o.weight + "#winograd_split");
+                r.flags |= f16w ? SBC_CONV_F16W : f16x2 ? SBC_CONV_F16X2 : 0;
+            }
+            // the exact modes: ELU keeps its relative accuracy for small inputs too
+            if (d.conv_mode <= 1 && (o.flags & SBC_PRO_ELU)) r.flags |= SBC_PRO_ELU_ACC;
+            break;
+        case SBC_OP_CONV_PAIR: case SBC_OP_CONV_POOL: case SBC_OP_RES_BLOCK:     // (the fused kernels read the direct fp16 forms only)
+            r.weight_split = need(o.weight + "#split");
+            r.weight_wino_split = calib(o.weight + "#winograd_split");
+            if (!o.weight2.empty()) {
+                r.weight2_split = need(o.weight2 + "#split");
+                r.weight2_wino_split = calib(o.weight2 + "#winograd_split");
+            }
+            r.bias2 = need(o.bias2); r.norm2 = need(o.norm2);
+            r.flags |= f16w && o.kind != SBC_OP_RES_BLOCK ? SBC_CONV_F16W : SBC_CONV_F16X2;
+            break;
+        case SBC_OP_CONV_DOWN:               // the pooled stride-2 filters; the layers' unpooled forms for the calibration
+            r.weight_split = need(o.weight + "#pool");
+            r.weight2_split = need(o.weight2 + "#pool");
+            r.bias2 = need(o.bias2);
+            r.weight = calib(o.weight + "#split");
+            r.weight_wino_split = calib(o.weight + "#winograd_split");
+            r.weight_wino = calib(o.weight2 + "#split");
+            r.flags |= SBC_CONV_F16X2;
+            break;
+        case SBC_OP_CHAIN: {
+            WIRE_REQUIRE(chains, "sbc_score_wiring_bind: the wiring has SBC_OP_CHAIN records, chains is NULL");
+            sbc_chain& ch = *chains++;
+            memset(&ch, 0, sizeof(ch));
+            ch.n_blocks = (int32_t)o.blocks.size();
+            for (size_t k = 0; k < o.blocks.size(); ++k) {
+                const Block& bl = o.blocks[k];
+                ch.type[k] = bl.type;
+                ch.w1[k] = need(bl.w1 + "#split"); ch.w2[k] = need(bl.w2 + "#split");
+                if (bl.dil == 1) {           // (a dilated layer runs in no Winograd launch at any array size: its form gets no scale)
+                    ch.w1_wino[k] = calib(bl.w1 + "#winograd_split"); ch.w2_wino[k] = calib(bl.w2 + "#winograd_split");
+                }
+                if (bl.type != SBC_CHAIN_RES) continue;
+                ch.dil[k] = bl.dil;
+                ch.bias1[k] = (const float*)need(bl.bias1); ch.bias2[k] = (const float*)need(bl.bias2);
+                ch.norm1[k] = (const float*)need(bl.norm1); ch.norm2[k] = (const float*)need(bl.norm2);
+                if (!bl.w3.empty()) { ch.w3[k] = need(bl.w3 + "#split"); ch.bias3[k] = (const float*)need(bl.bias3); }
+            }
+            r.ext = &ch;
+            r.flags |= SBC_CONV_F16X2;
+            break;
+        }
+        default:                             // begin / end convolution: torch layout; statistics: the norm's (alpha | gamma | beta)
+            r.weight = need(o.weight);
+            if (o.kind == SBC_OP_END_CONV) r.ext = d.endconv;
+        }
+        if (lacks) return SBC_ERR_INVALID;
     }
     return SBC_OK;
 }
@@ -508,8 +620,14 @@ int sbc_score_wiring_create(const sbc_score_wiring_desc* desc, sbc_score_wiring*
 int sbc_score_wiring_read(const sbc_score_wiring* s, sbc_score_wiring_view* view) {
     WIRE_REQUIRE(s && view, "sbc_score_wiring_read: handle or view is NULL");
     *view = {s->tensors.data(), s->records.data(), s->blocks.data(), s->slot_elems.data(), (int32_t)s->tensors.size(),
-             (int32_t)s->records.size(), (int32_t)s->blocks.size(), (int32_t)s->slot_elems.size(), s->w.x, s->w.out};
+             (int32_t)s->records.size(), (int32_t)s->blocks.size(), (int32_t)s->slot_elems.size(), s->w.x, s->w.out,
+             (int32_t)std::count_if(s->w.records.begin(), s->w.records.end(), [](const sbc::wire::Record& o) { return o.kind == SBC_OP_CHAIN; })};
     return SBC_OK;
+}
+
+int sbc_score_wiring_bind(const sbc_score_wiring* s, const sbc_score_bind_desc* desc, sbc_op* ops, sbc_chain* chains) {
+    WIRE_REQUIRE(s && desc, "sbc_score_wiring_bind: handle or desc is NULL");
+    return sbc::wire::bind(s->w, *desc, ops, chains);
 }
 
 void sbc_score_wiring_destroy(sbc_score_wiring* s) { delete s; }

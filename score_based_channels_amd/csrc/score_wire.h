@@ -1,7 +1,8 @@
 // The wiring of NCSNv2Deepest (ncsnv2/models/ncsnv2.py:269-300) into fused launch records: which records exist, in which order, on
-// which launch lane, and which logical tensors share storage.  Host only -- no HIP header, no device: score.hip binds the records to
-// device memory for a C host (sbc_score_create), plan.py reads them through sbc_score_wiring_* (include/sbc_hip.h) for the Python
-// host.  Every fusion rule, profiling tag and shape predicate of the network lives in this unit and nowhere else.
+// which launch lane, which logical tensors share storage -- and their binding: which packed form of which parameter goes into which
+// sbc_op field over a host's memory.  Host only -- no HIP header, no device: score.hip (sbc_score_create, a C host) and scorenet.py
+// (through sbc_score_wiring_*, include/sbc_hip.h) pack weights, allocate, and call bind().  Every fusion rule, profiling tag, shape
+// predicate, conv_mode gate and binding rule of the network lives in this unit and nowhere else.
 #pragma once
 #include <array>
 #include <string>
@@ -69,9 +70,11 @@ struct Wiring {
     int x = -1, out = -1;                    // the network's input and output tensors [nt][nr][channels]
 };
 
-// SBC_OK, or SBC_ERR_INVALID with the reason in sbc_last_error().  Wires what `d` asks for: which flags a conv_mode or an array
-// size allows is the caller's business (sbc_score_create, scorenet.ScoreNet.score_plan).
+// SBC_OK, or SBC_ERR_INVALID with the reason in sbc_last_error().  Wires what `d` asks for behind the gates of d.conv_mode
+// (include/sbc_hip.h); which SBC_SCORE_FUSE_* a mode can run is the caller's business (sbc_score_create, scorenet.ScoreNet).
 __attribute__((visibility("hidden"))) int build(const sbc_score_wiring_desc& d, Wiring& out);      // (the library exports the C calls only)
+// sbc_score_wiring_bind on a Wiring: ops [w.records.size()], chains [one per SBC_OP_CHAIN record]
+__attribute__((visibility("hidden"))) int bind(const Wiring& w, const sbc_score_bind_desc& d, sbc_op* ops, sbc_chain* chains);
 
 }  // namespace wire
 }  // namespace sbc

@@ -4,10 +4,11 @@
 the same dataflow is expressed as ~160 fused operator records (``Op``) over NHWC buffers -- one record per
 HIP launch of ``libsbc_hip.so`` (``include/sbc_hip.h``).  *What* is launched in which order and which logical tensors
 share storage is decided once, inside the library (``csrc/score_wire.cpp``: the fusion rules, the profiling tags, the
-launch lanes, the slot assignment -- the same unit ``sbc_score_create`` builds a C host's records from); this module reads
-that wiring through ``sbc_score_wiring_*`` into the dataclasses below.  It needs the built library and no device (no
-torch, no HIP call).  ``scorenet.py`` binds the records to device memory; ``tests/test_plan_cpu.py`` interprets the very same
-records with the CPU oracle's primitives to prove the wiring without a GPU.
+launch lanes, the slot assignment, the gates of a conv_mode -- the same unit ``sbc_score_create`` builds a C host's records from);
+this module reads that wiring through ``sbc_score_wiring_*`` into the dataclasses below and keeps its handle (``ScorePlan.wiring``).
+It needs the built library and no device (no torch, no HIP call).  ``scorenet.py`` hands the handle, its buffers and its packed
+weights to the library's binder (``sbc_score_wiring_bind``); ``tests/test_plan_cpu.py`` interprets the very same records with the
+CPU oracle's primitives to prove the wiring without a GPU.
 """
 import ctypes as C
 from dataclasses import dataclass, field
@@ -22,7 +23,6 @@ PRO_NORM_MOMENTS, EPI_MOMENTS_OUT = 0x4000, 0x8000
 EPI_RES1_ELU, EPI_POOL, EPI_UP, EPI_ELUGRAD = 0x010, 0x020, 0x040, 0x080
 CONV_F16W = 0x100
 CONV_F16X2 = 0x10000
-PRO_ELU_ACC = 0x20000         # ELU with fp32's relative accuracy for small negative inputs (include/sbc_hip.h)
 # training operators
 (DSM_PERTURB, DSM_LOSS, GRAD_ADD, INORM_BWD, MAXPOOL5_BWD, UPSAMPLE_BWD, POOL_BWD, CONV_WGRAD, PACK_WEIGHT, END_CONV_BWD,
  BEGIN_CONV_BWD, ADAM_EMA) = range(9, 21)
@@ -99,6 +99,17 @@ class Op:
         return [t for t in (self.dst, self.moments) if t is not None]
 
 
+class Wiring:
+    """Owner of an ``sbc_score_wiring`` handle: what ``sbc_score_wiring_bind`` is called on; freed with the last reference."""
+
+    def __init__(self, handle):
+        self.handle, self.n_chains = handle, 0       # n_chains: its SBC_OP_CHAIN records (one sbc_chain each)
+        self._destroy = _lib.lib().sbc_score_wiring_destroy
+
+    def __del__(self):
+        self._destroy(self.handle)
+
+
 @dataclass
 class ScorePlan:
     ops: List[Op]
@@ -106,11 +117,13 @@ class ScorePlan:
     out: Tensor               # network output [Nt][Nr][2]   (complex64 view of the score)
     tensors: List[Tensor]
     slot_elems: List[int] = field(default_factory=list)   # per-sample float32 elements of each physical slot
+    wiring: Optional[Wiring] = None     # the library's handle these lists were read from
 
 
-# (channels, width) of the RCU blocks the plan fuses into SBC_OP_CONV_PAIR launches (``fuse_pairs=True``: the library's own list, the same)
+# (channels, width) of the RCU blocks the library fuses into SBC_OP_CONV_PAIR launches with ``fuse_pairs=True``, and in the fp16-weight
+# mode (``conv_mode='f16w'``).  Nothing in the package passes them any more; the tests pass them as explicit tuples and hold the
+# library's own lists to them (tests/test_plan_golden_cpu.py).
 PAIR_SHAPES = ((32, 16),)
-# ... in the fp16-weight mode (BASELINE config 5, a 256 x 64 array): also 32-pixel and 64-pixel rows, and the 64-channel levels
 PAIR_SHAPES_F16W = ((32, 16), (32, 32), (32, 64), (64, 16), (64, 32))
 
 MAX_LANES, MAX_EVENTS = 4, 64
@@ -129,17 +142,20 @@ WIRING_OVERLAP, WIRING_PRIVATE_SLOTS = 0x100, 0x200
 
 
 def build_score_plan(ngf=32, nt=64, nr=16, channels=2, share_slots=True, overlap=False, fold_stats=False, fuse_pairs=False, fuse_res=False,
-                     fuse_chain=False, fuse_down=False, fuse_end=False, skip_overlap=None):
+                     fuse_chain=False, fuse_down=False, fuse_end=False, skip_overlap=None, conv_mode=None):
     """Op list of one ``NCSNv2Deepest.forward`` for ``[B, 2, nt, nr]`` inputs (ncsnv2.py:269-300), as the library wires it
-    (``sbc_score_wiring_create``; what each switch does: include/sbc_hip.h, csrc/score_wire.cpp).  ``fuse_pairs``: True, or a tuple of
-    (channels, width); ``skip_overlap``: True, or a spec like ``DEFAULT_SKIP_SPEC``; ``share_slots=False`` gives every logical tensor
-    its own storage (a training step reads every activation again on the way back, ``train.py``).  Raises ``ValueError`` with the
-    library's reason for what it refuses."""
+    (``sbc_score_wiring_create``; what each switch does: include/sbc_hip.h, csrc/score_wire.cpp).  ``fuse_pairs``: True (the library's
+    list of shapes), or a tuple of (channels, width); ``skip_overlap``: True, or a spec like ``DEFAULT_SKIP_SPEC``; ``share_slots=False``
+    gives every logical tensor its own storage (a training step reads every activation again on the way back, ``train.py``);
+    ``conv_mode``: None wires exactly what the switches ask for, a name of ``config.CONV_MODES`` puts that mode's gates in front (no
+    ``fold_stats`` in 'f32' or off powers of two, the longer list of pair shapes in 'f16w').  Raises ``ValueError`` with the library's
+    reason for what it refuses."""
     L = _lib.lib()
     switches = ((fuse_pairs, SCORE_FUSE_PAIRS), (fold_stats, SCORE_FOLD_STATS), (fuse_res, SCORE_FUSE_RES), (fuse_chain, SCORE_FUSE_CHAIN),
                 (fuse_down, SCORE_FUSE_DOWN), (fuse_end, SCORE_FUSE_END), (skip_overlap, SCORE_SKIP_LANES), (overlap, WIRING_OVERLAP),
                 (not share_slots, WIRING_PRIVATE_SLOTS))
-    desc = _lib.sbc_score_wiring_desc(ngf=ngf, channels=channels, nt=nt, nr=nr, flags=sum(bit for on, bit in switches if on))
+    desc = _lib.sbc_score_wiring_desc(ngf=ngf, channels=channels, nt=nt, nr=nr, flags=sum(bit for on, bit in switches if on),
+                                      conv_mode=-1 if conv_mode is None else _lib.CONV_MODE_IDS[conv_mode])
     if fuse_pairs and isinstance(fuse_pairs, tuple):
         desc.pair_shapes = (C.c_int32 * (2 * len(fuse_pairs)))(*[v for shape in fuse_pairs for v in shape])
         desc.n_pair_shapes = len(fuse_pairs)
@@ -149,27 +165,26 @@ def build_score_plan(ngf=32, nt=64, nr=16, channels=2, share_slots=True, overlap
     handle, view = C.c_void_p(), _lib.sbc_score_wiring_view()
     if L.sbc_score_wiring_create(C.byref(desc), C.byref(handle)):
         raise ValueError(L.sbc_last_error().decode())
-    try:
-        _lib.check(L.sbc_score_wiring_read(handle, C.byref(view)))
-        text = lambda b: None if b is None else b.decode()
-        tensors = [Tensor(text(t.name), t.h, t.w, t.c, t.slot) for t in view.tensors[:view.n_tensors]]
-        at = lambda i: None if i < 0 else tensors[i]
+    wiring = Wiring(handle)            # (owns the handle from here on, also when the read below raises)
+    _lib.check(L.sbc_score_wiring_read(handle, C.byref(view)))
+    wiring.n_chains = view.n_chains
+    text = lambda b: None if b is None else b.decode()
+    tensors = [Tensor(text(t.name), t.h, t.w, t.c, t.slot) for t in view.tensors[:view.n_tensors]]
+    at = lambda i: None if i < 0 else tensors[i]
 
-        def block(b):
-            extra = None
-            if b.type == CHAIN_RES:
-                extra = dict(dil=b.dil, **{k: text(getattr(b, k)) for k in ('bias1', 'bias2', 'norm1', 'norm2', 'w3', 'bias3')})
-            return (b.type, text(b.w1), text(b.w2), extra)
+    def block(b):
+        extra = None
+        if b.type == CHAIN_RES:
+            extra = dict(dil=b.dil, **{k: text(getattr(b, k)) for k in ('bias1', 'bias2', 'norm1', 'norm2', 'w3', 'bias3')})
+        return (b.type, text(b.w1), text(b.w2), extra)
 
-        ops = [Op(r.kind, text(r.name), src=at(r.src), dst=at(r.dst), weight=text(r.weight), weight2=text(r.weight2), bias2=text(r.bias2),
-                  norm2=text(r.norm2), bias=text(r.bias), stats=at(r.stats), res1=at(r.res1), res2=at(r.res2), up=at(r.up), flags=r.flags,
-                  ksize=r.ksize, dil=r.dil, tag=r.tag, side=bool(r.side), join=bool(r.join), moments=at(r.moments), geom=at(r.geom),
-                  norm_key=text(r.norm_key), blocks=[block(b) for b in view.blocks[r.first_block:r.first_block + r.n_blocks]] or None,
-                  lane=r.lane, signal=r.signal, wait=tuple(e for e in r.wait if e))
-               for r in view.records[:view.n_records]]
-        return ScorePlan(ops, tensors[view.x], tensors[view.out], tensors, list(view.slot_elems[:view.n_slots]))
-    finally:
-        L.sbc_score_wiring_destroy(handle)
+    ops = [Op(r.kind, text(r.name), src=at(r.src), dst=at(r.dst), weight=text(r.weight), weight2=text(r.weight2), bias2=text(r.bias2),
+              norm2=text(r.norm2), bias=text(r.bias), stats=at(r.stats), res1=at(r.res1), res2=at(r.res2), up=at(r.up), flags=r.flags,
+              ksize=r.ksize, dil=r.dil, tag=r.tag, side=bool(r.side), join=bool(r.join), moments=at(r.moments), geom=at(r.geom),
+              norm_key=text(r.norm_key), blocks=[block(b) for b in view.blocks[r.first_block:r.first_block + r.n_blocks]] or None,
+              lane=r.lane, signal=r.signal, wait=tuple(e for e in r.wait if e))
+           for r in view.records[:view.n_records]]
+    return ScorePlan(ops, tensors[view.x], tensors[view.out], tensors, list(view.slot_elems[:view.n_slots]), wiring)
 
 
 def chain_conv_count(op):

@@ -5,6 +5,10 @@ Interface kept from the reference call sites (``test_score.py:59-63,137,151``):
 ``ScoreNet(config)``, ``.cuda()``, ``.load_state_dict(contents['model_state'])``, ``.eval()``,
 ``.sigmas`` (float32 ``[num_classes]`` device tensor) and ``net(x[B,2,Nt,Nr], labels[B]) -> [B,2,Nt,Nr]``.
 torch is used for device memory and streams only; no torch operator computes anything on this path.
+
+What this host owns: which forms of the weights it packs (``load_state_dict``: every form of the selected multiplier, so that one
+buffer serves every array size), the buffers (``bind``), the calibration pass and which plan a batch takes.  Which records there are
+and which form goes into which ``sbc_op`` field is the library's (``plan.build_score_plan``, ``sbc_score_wiring_bind``).
 """
 import ctypes as C
 import os
@@ -29,7 +33,7 @@ class BoundScore:
 
     def __init__(self, ops, x, out, slots, labels, extra_keep, plan=None):
         self.plan = plan            # the plan.ScorePlan the records were made from (record k of ``ops`` is ``plan.ops[k]``)
-        self.ops = ops              # list of _lib.sbc_op (ctypes); END_CONV.ext points into ``extra_keep``
+        self.ops = ops              # list of _lib.sbc_op (ctypes views of one array); every ext points into ``extra_keep``
         self.x = x                  # float32 [B, Nt, Nr, 2]  (view as complex64 [B, Nt, Nr])
         self.out = out              # float32 [B, Nt, Nr, 2]
         self.slots = slots
@@ -126,6 +130,7 @@ class ScoreNet:
         self._sigmas_np = get_sigmas(config)
         self._wdev = None
         self._woff = {}
+        self._params = None             # (_wdev, its sbc_named_ptr table, the names' bytes): what bind hands the library's binder
         self._sigmas = None
         self._call_cache = {}
         self._plans = {}
@@ -257,9 +262,8 @@ class ScoreNet:
         the fused f16x2 plan) -- ``driver.batch_limit`` sizes chunks for the larger of the two.  Builds no device state."""
         key = ('fallback', nt, nr)
         if key not in self._plans:
-            fold = self.fold_stats and not (nt & (nt - 1)) and not (nr & (nr - 1))
-            self._plans[key] = sum(P.build_score_plan(self.ngf, nt, nr, self.channels, overlap=self.overlap, fold_stats=fold,
-                                                      fuse_pairs=False, fuse_res=False).slot_elems)
+            self._plans[key] = sum(P.build_score_plan(self.ngf, nt, nr, self.channels, overlap=self.overlap, fold_stats=self.fold_stats,
+                                                      conv_mode='bf16x3').slot_elems)
         return self._plans[key]
 
     # --- binding ----------------------------------------------------------------------------------
@@ -275,18 +279,18 @@ class ScoreNet:
         skip = self.skip_overlap_for(B, nt, nr) if lanes is None else (bool(lanes) and bool(self.skip_overlap) and not self.overlap)
         key = (nt, nr, skip)
         if key not in self._plans:
-            fold = self.fold_stats and not (nt & (nt - 1)) and not (nr & (nr - 1))     # conv_wx3 takes power-of-two images
-            self._plans[key] = P.build_score_plan(self.ngf, nt, nr, self.channels, overlap=self.overlap, fold_stats=fold,
-                                                  fuse_pairs=(P.PAIR_SHAPES_F16W if self.conv_mode == 'f16w' else P.PAIR_SHAPES) if self.fuse_pairs else False,
-                                                  fuse_res=self.fuse_res, fuse_chain=self.fuse_chain and not self.overlap,
+            # (what the array size and the multiplier rule out of these switches -- folded statistics off powers of two, the pair shapes
+            # of 'f16w' -- is the wiring's decision, conv_mode tells it)
+            self._plans[key] = P.build_score_plan(self.ngf, nt, nr, self.channels, overlap=self.overlap, fold_stats=self.fold_stats,
+                                                  fuse_pairs=self.fuse_pairs, fuse_res=self.fuse_res, fuse_chain=self.fuse_chain and not self.overlap,
                                                   fuse_down=self.fuse_down and not self.overlap, fuse_end=self.fuse_end,
-                                                  skip_overlap=(self.skip_overlap if skip else None))
+                                                  skip_overlap=(self.skip_overlap if skip else None), conv_mode=self.conv_mode)
         return self._plans[key]
 
     def bind(self, B, nt, nr, *, step=None, sigma_of_step=None, use_labels=True, lanes=None):
-        """Allocate buffers for batch ``B`` and translate the plan into ``sbc_op`` records.  ``lanes``: take the plan with launch
-        lanes (True) or the sequential one (False); default: by batch size (``skip_overlap_for``) -- a caller that runs several
-        sub-batches side by side passes False (``driver.stream_count``).
+        """Allocate buffers for batch ``B`` and have the library bind the plan's records to them and to the packed weights
+        (``sbc_score_wiring_bind``).  ``lanes``: take the plan with launch lanes (True) or the sequential one (False); default: by
+        batch size (``skip_overlap_for``) -- a caller that runs several sub-batches side by side passes False (``driver.stream_count``).
         Noise level source of the end conv: per-sample ``labels`` (module-call semantics) or the device step
         counter + ``sigma_of_step`` table (inside an ALD plan)."""
         if self._wdev is None:
@@ -300,105 +304,20 @@ class ScoreNet:
                                labels=_ptr(labels) if use_labels else None,
                                sigma_of_step=_ptr(sigma_of_step) if sigma_of_step is not None else None,
                                step=_ptr(step) if step is not None else None)
-        ops = []
-        keep = []                                                            # ext structs the records point at
-        for op in pl.ops:
-            o = _lib.sbc_op()
-            shape = op.geom if op.geom is not None else op.src              # (statistics from tile moments: the image's dims)
-            o.kind, o.flags, o.B, o.H, o.W = op.kind, op.flags, B, shape.h, shape.w
-            o.flags |= (P.OP_SIDE if op.side else 0) | (P.OP_JOIN if op.join else 0)
-            o.cin, o.cout, o.ksize, o.dil, o.tag = shape.c, op.dst.c, op.ksize, op.dil, op.tag
-            o.lane, o.signal = op.lane, op.signal
-            for k, e in enumerate(op.wait):
-                o.wait[k] = e
-            o.in_ = _ptr(slots[op.src.slot])
-            o.out = _ptr(slots[op.dst.slot])
-            # (fused records in f16x2 also carry the layers' Winograd forms: no fused kernel reads them, sbc_f16x2_calibrate writes the
-            # activation scale into every form of a layer -- this weight buffer is shared by every array size the net is bound at)
-            wino = (lambda key: _ptr(self._wdev, self._woff[key + '#winograd_split'])) if self.conv_mode == 'f16x2' else (lambda key: None)
-            if op.kind == P.CONV_PAIR:
-                o.ksize, o.dil = 3, 1
-                o.weight_split = _ptr(self._wdev, self._woff[op.weight + '#split'])
-                o.weight2_split = _ptr(self._wdev, self._woff[op.weight2 + '#split'])
-                o.weight_wino_split, o.weight2_wino_split = wino(op.weight), wino(op.weight2)
-                o.flags |= P.CONV_F16W if self.conv_mode == 'f16w' else P.CONV_F16X2
-            elif op.kind == P.CONV_POOL:
-                o.ksize, o.dil = 3, 1
-                o.weight_split = _ptr(self._wdev, self._woff[op.weight + '#split'])
-                o.weight_wino_split = wino(op.weight)
-                o.flags |= P.CONV_F16W if self.conv_mode == 'f16w' else P.CONV_F16X2
-            elif op.kind == P.CONV_DOWN:
-                o.ksize, o.dil = 3, 1
-                o.weight_split = _ptr(self._wdev, self._woff[op.weight + '#pool'])
-                o.weight2_split = _ptr(self._wdev, self._woff[op.weight2 + '#pool'])
-                # calibration only (include/sbc_hip.h: SBC_OP_CONV_DOWN): the two layers' unpooled forms, read by the unfused launches
-                # of an array size at which the block is not down-fusable
-                o.weight = _ptr(self._wdev, self._woff[op.weight + '#split'])
-                o.weight_wino_split = wino(op.weight)
-                o.weight_wino = _ptr(self._wdev, self._woff[op.weight2 + '#split'])
-                o.bias2 = _ptr(self._wdev, self._woff[op.bias2])
-                o.flags |= P.CONV_F16X2
-            elif op.kind == P.CHAIN:
-                o.ksize, o.dil = 3, 1
-                ch = _lib.sbc_chain(n_blocks=len(op.blocks))
-                for k, (typ, k1, k2, ex) in enumerate(op.blocks):
-                    ch.type[k] = typ
-                    ch.w1[k], ch.w2[k] = _ptr(self._wdev, self._woff[k1 + '#split']), _ptr(self._wdev, self._woff[k2 + '#split'])
-                    if ex is None or ex['dil'] == 1:                # (dilated layers have no Winograd form)
-                        ch.w1_wino[k], ch.w2_wino[k] = wino(k1), wino(k2)
-                    if ex is not None:
-                        ch.dil[k] = ex['dil']
-                        ch.bias1[k], ch.bias2[k] = _ptr(self._wdev, self._woff[ex['bias1']]), _ptr(self._wdev, self._woff[ex['bias2']])
-                        ch.norm1[k], ch.norm2[k] = _ptr(self._wdev, self._woff[ex['norm1']]), _ptr(self._wdev, self._woff[ex['norm2']])
-                        if ex['w3'] is not None:
-                            ch.w3[k], ch.bias3[k] = _ptr(self._wdev, self._woff[ex['w3'] + '#split']), _ptr(self._wdev, self._woff[ex['bias3']])
-                keep.append(ch)
-                o.ext = C.cast(C.pointer(ch), C.c_void_p)
-                o.flags |= P.CONV_F16X2
-            elif op.kind == P.RES_BLOCK:
-                o.ksize, o.dil = 3, 1
-                o.weight_split = _ptr(self._wdev, self._woff[op.weight + '#split'])
-                o.weight2_split = _ptr(self._wdev, self._woff[op.weight2 + '#split'])
-                o.weight_wino_split, o.weight2_wino_split = wino(op.weight), wino(op.weight2)
-                o.bias2 = _ptr(self._wdev, self._woff[op.bias2])
-                o.norm2 = _ptr(self._wdev, self._woff[op.norm2])
-                o.flags |= P.CONV_F16X2
-            elif op.weight is not None and op.kind != P.CONV:
-                o.weight = _ptr(self._wdev, self._woff[op.weight])
-            elif op.weight is not None and self.conv_mode == 'f32':
-                o.weight = _ptr(self._wdev, self._woff[op.weight])
-                if op.ksize == 3 and op.dil == 1:
-                    o.weight_wino = _ptr(self._wdev, self._woff[op.weight + '#winograd'])
-            elif op.weight is not None:
-                o.weight_split = _ptr(self._wdev, self._woff[op.weight + '#split'])
-                if op.ksize == 3 and op.dil == 1:
-                    o.weight_wino_split = _ptr(self._wdev, self._woff[op.weight + '#winograd_split'])
-                if self.conv_mode == 'f16w':
-                    o.flags |= P.CONV_F16W
-                elif self.conv_mode == 'f16x2':
-                    o.flags |= P.CONV_F16X2
-            if self.conv_mode in ('bf16x3', 'f32') and op.kind == P.CONV and op.flags & P.PRO_ELU:
-                o.flags |= P.PRO_ELU_ACC          # the exact modes: ELU keeps its relative accuracy for small inputs too
-            if op.bias is not None:
-                o.bias = _ptr(self._wdev, self._woff[op.bias])
-            if op.stats is not None:
-                o.stats = _ptr(slots[op.stats.slot])
-            if op.norm_key is not None:                                 # PRO_NORM_SELF: the norm's (alpha | gamma | beta)
-                o.stats = _ptr(self._wdev, self._woff[op.norm_key])
-            if op.moments is not None:
-                o.aux = _ptr(slots[op.moments.slot])
-            if op.res1 is not None:
-                o.res1 = _ptr(slots[op.res1.slot])
-            if op.res2 is not None:
-                o.res2 = _ptr(slots[op.res2.slot])
-            if op.up is not None:
-                o.up, o.up_h, o.up_w = _ptr(slots[op.up.slot]), op.up.h, op.up.w
-            if op.kind == P.END_CONV:
-                o.ext = C.cast(C.pointer(ext), C.c_void_p)
-            ops.append(o)
+        if self._params is None or self._params[0] is not self._wdev:
+            # what load_state_dict packed, by name (the keys of _woff), for the library's binder: once per loaded state dict
+            names, base = [k.encode() for k in self._woff], self._wdev.data_ptr()
+            table = (_lib.sbc_named_ptr * len(names))(*[_lib.sbc_named_ptr(n, base + 4 * off) for n, off in zip(names, self._woff.values())])
+            self._params = (self._wdev, table, names)
+        table = self._params[1]
+        # which form goes into which field of which record: csrc/score_wire.cpp (sbc_score_wiring_bind), the same call a C host's records come from
+        ops, chains = (_lib.sbc_op * len(pl.ops))(), (_lib.sbc_chain * pl.wiring.n_chains)()
+        desc = _lib.sbc_score_bind_desc(batch=B, conv_mode=_lib.CONV_MODE_IDS[self.conv_mode], slots=(C.c_void_p * len(slots))(*[t.data_ptr() for t in slots]),
+                                        n_slots=len(slots), params=table, n_params=len(table), endconv=C.pointer(ext))
+        _lib.check(_lib.lib().sbc_score_wiring_bind(pl.wiring.handle, C.byref(desc), ops, chains))
         x = slots[pl.x.slot].view(B, nt, nr, self.channels)
         out = slots[pl.out.slot].view(B, nt, nr, self.channels)
-        return BoundScore(ops, x, out, slots, labels, [ext, self._wdev, self.sigmas, sigma_of_step, step, keep], plan=pl)
+        return BoundScore(list(ops), x, out, slots, labels, [ext, self._wdev, self.sigmas, sigma_of_step, step, (ops, chains)], plan=pl)
 
     # --- module call --------------------------------------------------------------------------------
     def __call__(self, x, labels):

@@ -1,8 +1,9 @@
 """The self-sufficient C boundary (``sbc_score_*``, include/sbc_hip.h): a host that is not Python gets the whole score
-network from the checkpoint tensors in one call.  Both hosts take their records from the library's one wiring (csrc/score_wire.cpp;
-tests/test_plan_golden_cpu.py holds it); what is held to the Python host (scorenet.py) here is the rest of ``sbc_score_create`` -- the
-gates it puts in front of the wiring, weight packing, record binding, calibration: identical operator records, bit-identical outputs,
-and a full Langevin-step plan composed from ``sbc_score_ops``.  ``pytest -m gpu``."""
+network from the checkpoint tensors in one call.  Both hosts take their records from the library's one wiring and one binder
+(csrc/score_wire.cpp; tests/test_plan_golden_cpu.py and tests/test_bind_golden_cpu.py hold them); what is held to the Python host
+(scorenet.py) here is the rest of ``sbc_score_create`` -- the gates it puts in front of the wiring, weight packing, the choice of
+forms it packs, calibration: identical operator records, bit-identical outputs, and a full Langevin-step plan composed from
+``sbc_score_ops``.  ``pytest -m gpu``."""
 import ctypes as C
 
 import numpy as np

@@ -42,9 +42,9 @@ def test_records_and_tensors_share_objects():
     assert pl.ops[1].src is pl.ops[0].moments and pl.ops[1].geom is pl.ops[0].dst            # (statistics from the begin convolution's tile moments)
 
 
-def _wiring_dump(nt, nr, flags):
-    """Canonical dump of the wiring the library builds from ``flags`` alone (its own shape list and skip branches)."""
-    desc = _lib.sbc_score_wiring_desc(ngf=32, channels=2, nt=nt, nr=nr, flags=flags)
+def _wiring_dump(nt, nr, flags, conv_mode):
+    """Canonical dump of the wiring the library builds from ``flags`` and ``conv_mode`` alone (its own shape list and skip branches)."""
+    desc = _lib.sbc_score_wiring_desc(ngf=32, channels=2, nt=nt, nr=nr, flags=flags, conv_mode=conv_mode)
     h, view = C.c_void_p(), _lib.sbc_score_wiring_view()
     _lib.check(_lib.lib().sbc_score_wiring_create(C.byref(desc), C.byref(h)))
     try:
@@ -57,18 +57,20 @@ def _wiring_dump(nt, nr, flags):
 
 def test_the_librarys_default_lists_are_the_python_constants():
     """``fuse_pairs=True`` / ``skip_overlap=True`` (the library's lists, what sbc_score_create uses) against plan.PAIR_SHAPES /
-    plan.DEFAULT_SKIP_SPEC passed explicitly; SBC_WIRING_PAIRS_F16W (sbc_score_create in conv_mode 2) against plan.PAIR_SHAPES_F16W,
-    at 64x16 and 256x64, which between them use every shape of that list."""
+    plan.DEFAULT_SKIP_SPEC passed explicitly, with no conv_mode and in every mode but 'f16w'; conv_mode 2 (sbc_score_create, and
+    ScoreNet in 'f16w') against plan.PAIR_SHAPES_F16W, at 64x16 and 256x64, which between them use every shape of that list."""
     kw = dict(fold_stats=True, fuse_res=True, fuse_chain=True, fuse_down=True, fuse_end=True)
     for nt, nr in ((64, 16), (256, 64)):
-        a = P.build_score_plan(32, nt, nr, fuse_pairs=True, skip_overlap=True, **kw)
-        b = P.build_score_plan(32, nt, nr, fuse_pairs=P.PAIR_SHAPES, skip_overlap=P.DEFAULT_SKIP_SPEC, **kw)
-        assert plan_dump.dump(a) == plan_dump.dump(b)
+        for mode in (None, 'bf16x3', 'f16x2'):
+            a = P.build_score_plan(32, nt, nr, fuse_pairs=True, skip_overlap=True, conv_mode=mode, **kw)
+            b = P.build_score_plan(32, nt, nr, fuse_pairs=P.PAIR_SHAPES, skip_overlap=P.DEFAULT_SKIP_SPEC, **kw)
+            assert plan_dump.dump(a) == plan_dump.dump(b)
     seen = set()
     for nt, nr in ((64, 16), (256, 64)):
         wide = P.build_score_plan(32, nt, nr, fuse_pairs=P.PAIR_SHAPES_F16W)
+        assert plan_dump.dump(wide) == plan_dump.dump(P.build_score_plan(32, nt, nr, fuse_pairs=True, conv_mode='f16w'))
         seen |= {(o.src.c, o.src.w) for o in wide.ops if o.kind == P.CONV_PAIR}
-        tensors, records = _wiring_dump(nt, nr, P.SCORE_FUSE_PAIRS | 0x400)          # SBC_WIRING_PAIRS_F16W
+        tensors, records = _wiring_dump(nt, nr, P.SCORE_FUSE_PAIRS, 2)
         index = {id(t): i for i, t in enumerate(wide.tensors)}
         assert tensors == [(t.name.encode(), t.h, t.w, t.c, t.slot) for t in wide.tensors]
         assert records == [(o.kind, o.name.encode(), index[id(o.src)], index[id(o.dst)], o.tag, o.lane, o.signal, (tuple(o.wait) + (0, 0))[:2])
@@ -78,6 +80,24 @@ def test_the_librarys_default_lists_are_the_python_constants():
     chains += [o for o in P.build_score_plan(32, 256, 64, fuse_chain=True).ops if o.kind == P.CHAIN]
     assert chains and all(o.tag == P.TAG_CHAIN + P.CHAIN_KERNELS.index((o.src.c, o.src.w)) for o in chains)
     assert {o.tag - P.TAG_CHAIN for o in chains} == set(range(len(P.CHAIN_KERNELS)))
+
+
+def test_a_conv_mode_puts_its_gates_in_front_of_the_switches():
+    """``conv_mode`` (sbc_score_wiring_desc.conv_mode 0 .. 3): folded statistics are dropped in 'f32' and for Nt or Nr that are no powers
+    of two, and nothing else changes; without a mode the switches are taken as they are (the golden matrix; the trainer)."""
+    same = lambda a, b: plan_dump.dump(a) == plan_dump.dump(b)
+    for nt, nr in ((64, 16), (48, 16), (96, 32), (128, 8)):
+        pow2 = not (nt & (nt - 1) or nr & (nr - 1))
+        folded, plain = P.build_score_plan(32, nt, nr, fold_stats=True), P.build_score_plan(32, nt, nr)
+        assert not same(folded, plain)
+        for mode in ('bf16x3', 'f16w', 'f16x2'):
+            assert same(P.build_score_plan(32, nt, nr, fold_stats=True, conv_mode=mode), folded if pow2 else plain)
+            assert same(P.build_score_plan(32, nt, nr, conv_mode=mode), plain)
+        assert same(P.build_score_plan(32, nt, nr, fold_stats=True, conv_mode='f32'), plain)
+    with pytest.raises(KeyError):
+        P.build_score_plan(32, 64, 16, conv_mode='fp8')
+    desc = _lib.sbc_score_wiring_desc(ngf=32, channels=2, nt=64, nr=16, conv_mode=4)
+    assert _lib.lib().sbc_score_wiring_create(C.byref(desc), C.byref(C.c_void_p())) == -1 and b'conv_mode' in _lib.lib().sbc_last_error()
 
 
 def test_the_librarys_tags_are_the_python_constants():
