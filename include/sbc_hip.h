@@ -858,6 +858,99 @@ int sbc_wgan_bn_backward(const float* gact, const float* raw, const int32_t* mas
 int sbc_wgan_rmsprop(float* p, const float* g, float* sq, int64_t n, double lr, double alpha, double eps, double clamp_lower, double clamp_upper,
                      int32_t mode, void* stream);
 
+/* ---- Coded link simulation (csrc/link.hip; link.py, test_end_to_end.py) ----------------------------------------------------
+ * What a channel estimate is worth to a receiver (matlab/test_end_to_end.m, testPackets.m, ComputeLLRMIMO.m 'ml'): packets of one
+ * quasi-cyclic LDPC codeword each, QPSK on S spatial streams, exhaustive ML soft demapping once with the ideal and once with the
+ * estimated precoded channel, sum-product decoding, BER / BLER per packet.  Exact fp32.  Purely additive to ABI 16.
+ *
+ *   sbc_link_code_create   base [rows][cols] circulant shifts (-1 = zero block), lifting size Z, interleaver P [N] (0-based:
+ *                          bitsInt[i] = bitsEnc[P[i]]); N = cols Z, M = rows Z, K = N - M.  The handle owns the bit-packed generator
+ *                          B^-1 A (H = [A | B]; the codeword is [payload; parity] with H c = 0), the edge tables and the workspace of
+ *                          sbc_link_simulate, on the current device.  SBC_ERR_UNSUPPORTED: singular B, N > 8192, a check of degree
+ *                          > 8 or < 2, more than 32768 edges.
+ *   sbc_link_encode        payload [Npk][K] bytes 0 / 1 -> codeword [Npk][N] bytes (or NULL) and symbols [Npk][uses][S] complex64,
+ *                          uses = floor(N / 2S): interleave, drop the N - 2 S uses tail bits, QPSK (first bit of a pair = MSB; integers
+ *                          0, 1, 2, 3 -> (-1+j, -1-j, 1+j, 1-j) / sqrt 2); symbol k is stream k mod S of use k div S.
+ *   sbc_link_llr           y = Hp_ideal[idx] x + sqrt(noise_power) w per channel use, then for Hp_ideal and Hp_est, every stream and
+ *                          bit  log(sum_{s: bit = 0} exp(-|y - Hp s|^2 / noise_power) / sum_{s: bit = 1} ...)  over all 4^S candidates, each
+ *                          class as a log-sum-exp around its smallest metric; flattened bit + 2 stream + 2S use, padded with zeros,
+ *                          deinterleaved (out[P[j]] = flat[j]) and, unless SBC_LINK_NO_CLIP, clipped |l| >= 6 -> +-6.  Hp [pool][Nr][S]
+ *                          complex64 (H Pt), chan_index [Npk][uses] int32 in [0, pool) (an index outside gives NaN soft bits, no read
+ *                          out of bounds), w [Npk][uses][Nr] standard CN(0, 1).  S in {2, 4}, 1 <= Nr <= 64.
+ *   sbc_link_decode        flooding sum-product on llr [Npk][N], check nodes in the exact pairwise form
+ *                          a [+] b = sign a sign b min(|a|, |b|) + log1p(e^-|a+b|) - log1p(e^-|a-b|) as a forward / backward recursion;
+ *                          at most max_iters iterations, with early_stop != 0 a codeword stops after the first iteration whose hard
+ *                          decisions (total < 0 -> 1) satisfy every check.  soft [Npk][K]; totals [Npk][N] and iters [Npk] or NULL.
+ *   sbc_link_errors        payload_hat = (sign(-soft) + 1) / 2 against payload: ber [Npk] (a soft output of 0 is an error), bler [Npk].
+ *   sbc_link_simulate      encode -> llr -> decode x 2 -> errors for one chunk of packets at one SNR point, on the handle's workspace
+ *                          (grown, with a device synchronisation, only when a larger chunk than ever before arrives).
+ *
+ * Randomness: caller buffers (payload, chan_index, noise are inputs), or with SBC_LINK_DEVICE_RANDOM the library's Philox4x32-10,
+ * key = seed, counter (q, 4 snr_index + purpose, packet lo, packet hi) with packet = packet0 + position in the chunk -- a packet's draws
+ * do not depend on chunking.  purpose 0: payload bit k = bit (k & 31) of word (k >> 5) & 3 of block q = k >> 7;  purpose 1: draw t = word
+ * t & 3 of block t >> 2, index = (draw * pool) >> 32, without replacement when pool >= uses (a draw that repeats an earlier index of the
+ * packet is skipped) and with replacement otherwise;  purpose 2: w of element e = use Nr + r as csrc/philox.h::complex_normal.  The
+ * buffers are then outputs (noise may be NULL).  noise.py::link_streams replays them on the host.
+ * Every launch is asynchronous on `stream`; every descriptor is checked before the first launch.  A packet's results are bit-identical
+ * whatever the chunk and its position in it. */
+#define SBC_LINK_DEVICE_RANDOM 1
+#define SBC_LINK_NO_CLIP 2
+typedef struct sbc_link_code sbc_link_code;
+typedef struct sbc_link_code_desc {
+    const int32_t* base;           /* [rows][cols]                                                              */
+    const int32_t* interleaver;    /* [cols * Z]                                                                */
+    int32_t rows, cols, Z;
+} sbc_link_code_desc;
+typedef struct sbc_link_random {
+    uint64_t seed;
+    int64_t packet0;               /* global index of the chunk's first packet                                  */
+    int32_t snr_index;
+    int32_t flags;                 /* SBC_LINK_DEVICE_RANDOM | SBC_LINK_NO_CLIP                                   */
+} sbc_link_random;
+typedef struct sbc_link_encode_desc {
+    void* payload;                 /* [Npk][K] uint8: in, or out with SBC_LINK_DEVICE_RANDOM                    */
+    void* codeword;                /* [Npk][N] uint8 out, or NULL                                               */
+    void* symbols;                 /* [Npk][uses][S] complex64 out                                              */
+    int32_t Npk, S;
+    sbc_link_random rnd;
+} sbc_link_encode_desc;
+typedef struct sbc_link_llr_desc {
+    const void* symbols;           /* [Npk][uses][S] complex64                                                  */
+    const void* Hp_ideal;          /* [pool][Nr][S] complex64                                                   */
+    const void* Hp_est;            /* [pool][Nr][S] complex64                                                   */
+    void* chan_index;              /* [Npk][uses] int32: in, or out with SBC_LINK_DEVICE_RANDOM                 */
+    void* noise;                   /* [Npk][uses][Nr] complex64: in, or out / NULL with SBC_LINK_DEVICE_RANDOM  */
+    void* llr_ideal;               /* [Npk][N] float out                                                        */
+    void* llr_est;                 /* [Npk][N] float out                                                        */
+    float noise_power;
+    int32_t Npk, pool, Nr, S;
+    sbc_link_random rnd;
+} sbc_link_llr_desc;
+typedef struct sbc_link_sim_desc {
+    const void* Hp_ideal;
+    const void* Hp_est;
+    void* payload;                 /* as sbc_link_encode_desc                                                   */
+    void* chan_index;              /* as sbc_link_llr_desc                                                      */
+    void* noise;
+    void* ber_ideal;               /* [Npk] float out, each                                                     */
+    void* bler_ideal;
+    void* ber_est;
+    void* bler_est;
+    void* iters_ideal;             /* [Npk] int32 out or NULL, each                                             */
+    void* iters_est;
+    float noise_power;
+    int32_t Npk, pool, Nr, S, max_iters;
+    sbc_link_random rnd;
+} sbc_link_sim_desc;
+int sbc_link_code_create(const sbc_link_code_desc* desc, sbc_link_code** out);
+void sbc_link_code_destroy(sbc_link_code* code);
+int sbc_link_encode(sbc_link_code* code, const sbc_link_encode_desc* desc, void* stream);
+int sbc_link_llr(sbc_link_code* code, const sbc_link_llr_desc* desc, void* stream);
+int sbc_link_decode(sbc_link_code* code, const float* llr, int32_t Npk, int32_t max_iters, int32_t early_stop, float* soft, float* totals,
+                    int32_t* iters, void* stream);
+int sbc_link_errors(sbc_link_code* code, const float* soft, const void* payload, int32_t Npk, float* ber, float* bler, void* stream);
+int sbc_link_simulate(sbc_link_code* code, const sbc_link_sim_desc* desc, void* stream);
+
 /* ---- Environment variables -------------------------------------------------------------------------------------------------
  * Everything the library (csrc/) and the Python host (score_based_channels_amd/) read from the environment, in ONE place.  None of them
  * changes a result beyond the stated tolerance of the tests that set them; they configure the process or are needed by a test or by

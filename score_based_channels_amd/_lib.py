@@ -24,7 +24,9 @@ EXPORTS = ('sbc_abi_version', 'sbc_set_persistent_cus', 'sbc_last_error', 'sbc_d
            'sbc_wgan_create', 'sbc_wgan_destroy', 'sbc_wgan_workspace_floats', 'sbc_wgan_generate', 'sbc_wgan_run', 'sbc_wgan_stage',
            'sbc_wgan_trainer_create', 'sbc_wgan_trainer_destroy', 'sbc_wgan_trainer_workspace_floats', 'sbc_wgan_trainer_critic_step',
            'sbc_wgan_trainer_generator_step', 'sbc_wgan_trainer_stage', 'sbc_wgan_trainer_copy', 'sbc_wgan_wgrad128_scratch_floats',
-           'sbc_wgan_wgrad128', 'sbc_wgan_bn_backward', 'sbc_wgan_rmsprop')
+           'sbc_wgan_wgrad128', 'sbc_wgan_bn_backward', 'sbc_wgan_rmsprop',
+           'sbc_link_code_create', 'sbc_link_code_destroy', 'sbc_link_encode', 'sbc_link_llr', 'sbc_link_decode', 'sbc_link_errors',
+           'sbc_link_simulate')
 
 
 class SbcError(RuntimeError):
@@ -169,6 +171,36 @@ class sbc_wgan_trainer_desc(C.Structure):
                 ('clamp_upper', C.c_double)]
 
 
+# coded link simulation (link.py)
+LINK_DEVICE_RANDOM, LINK_NO_CLIP = 1, 2
+
+
+class sbc_link_code_desc(C.Structure):
+    _fields_ = [('base', C.c_void_p), ('interleaver', C.c_void_p), ('rows', C.c_int32), ('cols', C.c_int32), ('Z', C.c_int32)]
+
+
+class sbc_link_random(C.Structure):
+    _fields_ = [('seed', C.c_uint64), ('packet0', C.c_int64), ('snr_index', C.c_int32), ('flags', C.c_int32)]
+
+
+class sbc_link_encode_desc(C.Structure):
+    _fields_ = [('payload', C.c_void_p), ('codeword', C.c_void_p), ('symbols', C.c_void_p), ('Npk', C.c_int32), ('S', C.c_int32),
+                ('rnd', sbc_link_random)]
+
+
+class sbc_link_llr_desc(C.Structure):
+    _fields_ = [('symbols', C.c_void_p), ('Hp_ideal', C.c_void_p), ('Hp_est', C.c_void_p), ('chan_index', C.c_void_p), ('noise', C.c_void_p),
+                ('llr_ideal', C.c_void_p), ('llr_est', C.c_void_p), ('noise_power', C.c_float), ('Npk', C.c_int32), ('pool', C.c_int32),
+                ('Nr', C.c_int32), ('S', C.c_int32), ('rnd', sbc_link_random)]
+
+
+class sbc_link_sim_desc(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ('Hp_ideal', 'Hp_est', 'payload', 'chan_index', 'noise', 'ber_ideal', 'bler_ideal', 'ber_est',
+                                          'bler_est', 'iters_ideal', 'iters_est')] + \
+               [('noise_power', C.c_float), ('Npk', C.c_int32), ('pool', C.c_int32), ('Nr', C.c_int32), ('S', C.c_int32),
+                ('max_iters', C.c_int32), ('rnd', sbc_link_random)]
+
+
 _lib = None
 
 
@@ -255,6 +287,14 @@ def lib():
     h.sbc_wgan_wgrad128.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 5 + [C.c_void_p]
     h.sbc_wgan_bn_backward.argtypes = [C.c_void_p] * 6 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]
     h.sbc_wgan_rmsprop.argtypes = [C.c_void_p] * 3 + [C.c_int64] + [C.c_double] * 5 + [C.c_int32, C.c_void_p]
+    h.sbc_link_code_create.argtypes = [C.POINTER(sbc_link_code_desc), C.POINTER(C.c_void_p)]
+    h.sbc_link_code_destroy.argtypes = [C.c_void_p]
+    h.sbc_link_code_destroy.restype = None
+    h.sbc_link_encode.argtypes = [C.c_void_p, C.POINTER(sbc_link_encode_desc), C.c_void_p]
+    h.sbc_link_llr.argtypes = [C.c_void_p, C.POINTER(sbc_link_llr_desc), C.c_void_p]
+    h.sbc_link_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    h.sbc_link_errors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    h.sbc_link_simulate.argtypes = [C.c_void_p, C.POINTER(sbc_link_sim_desc), C.c_void_p]
     if h.sbc_abi_version() != ABI_VERSION:
         raise SbcError('libsbc_hip.so ABI %d != expected %d' % (h.sbc_abi_version(), ABI_VERSION))
     _lib = h
