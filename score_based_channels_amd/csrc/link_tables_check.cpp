@@ -1,6 +1,6 @@
 // Stand-alone host program for `make check-link`: builds the generator and edge tables of link_tables.h under the address and
-// undefined-behaviour sanitizers -- the 802.11n (648, 324) code of the reference, a small code with uneven check degrees, and every
-// refusal -- and checks what link.hip relies on: H c = 0 for encoded payloads, every edge listed once per side, sorted lists.
+// undefined-behaviour sanitizers -- the 802.11n (648, 324) code of the reference and its base at Z = 56, a small code with uneven check degrees
+// at three sizes, one with check degrees 2, 5, 6 and 7, and every refusal -- and checks what link.hip relies on: H c = 0 for encoded payloads, every edge listed once per side, sorted lists.
 #include "link_tables.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -28,6 +28,8 @@ static const int32_t REF_BASE[12 * 24] = {
     25, -1, 8, -1, 23, 18, -1, 14, 9, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0, 0,
     3, -1, -1, -1, 16, -1, -1, 2, 25, 5, -1, -1, 1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0};
 static const int32_t SMALL_BASE[3 * 6] = {0, 1, -1, 0, -1, -1, 2, -1, 3, 0, 0, -1, -1, 4, 1, -1, 0, 0};
+// check degrees 2, 5, 6, 7 and variable degrees 1 .. 4 (tests/link_cases.py)
+static const int32_t MIXED_BASE[4 * 8] = {3, -1, -1, -1, 0, -1, -1, -1, 1, 2, 0, -1, 4, 0, -1, -1, 0, 4, 1, 2, -1, 3, 0, -1, 2, 0, 3, 1, 1, -1, 2, 0};
 
 static std::vector<int32_t> reversed_interleaver(int N) {
     std::vector<int32_t> p(N);
@@ -89,6 +91,9 @@ int main() {
     check_code(REF_BASE, 12, 24, 27, 2376, 8, 12);
     check_code(SMALL_BASE, 3, 6, 5, 55, 4, 2);
     check_code(SMALL_BASE, 3, 6, 10, 110, 4, 2);
+    check_code(MIXED_BASE, 4, 8, 7, 140, 7, 4);
+    check_code(REF_BASE, 12, 24, 56, 4928, 8, 12);                               // one codeword per decoder workgroup
+    check_code(SMALL_BASE, 3, 6, 120, 1320, 4, 2);
     const std::vector<int32_t> P30 = reversed_interleaver(30);
     std::vector<int32_t> twice = P30;
     twice[3] = twice[4];
@@ -109,6 +114,6 @@ int main() {
     const std::vector<int32_t> Pbig = reversed_interleaver(24 * 400);
     check_refusal(big.data(), 2, 24, 400, Pbig.data(), 2);                       // more than 8192 bits
     if (failures) { printf("%d check(s) failed\n", failures); return 1; }
-    printf("link tables: 3 codes and 9 refusals built and freed clean\n");
+    printf("link tables: 6 codes and 9 refusals built and freed clean\n");
     return 0;
 }

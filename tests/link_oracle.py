@@ -172,10 +172,14 @@ class Graph:
 
 
 def boxplus(a, b):
-    """The exact pairwise check-node form in the dtype of its operands."""
+    """The exact pairwise check-node form in the dtype of its operands.  +inf (the pad of a check with fewer edges than the largest
+    degree) is the neutral element: a [+] inf = a, also where both operands are pads (the formula alone gives inf - inf = NaN
+    there, which a check more than one edge short of the largest degree then carries into its backward recursion)."""
     t = a.dtype.type
-    return (np.sign(a) * np.sign(b) * np.minimum(np.abs(a), np.abs(b)) + np.log1p(np.exp(-np.abs(a + b)))
-            - np.log1p(np.exp(-np.abs(a - b)))).astype(t)
+    with np.errstate(invalid='ignore'):
+        r = (np.sign(a) * np.sign(b) * np.minimum(np.abs(a), np.abs(b)) + np.log1p(np.exp(-np.abs(a + b)))
+             - np.log1p(np.exp(-np.abs(a - b)))).astype(t)
+    return np.where(b == np.inf, a, np.where(a == np.inf, b, r))
 
 
 def _check_update(m, g, dtype):

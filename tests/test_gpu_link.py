@@ -2,131 +2,16 @@
 numpy restatement of the reference's MATLAB scripts (tests/link_oracle.py) on the inputs of tests/link_cases.py.  float64 (tanh /
 atanh decoder, plain exp sums) is the yardstick; the float32 restatement (pairwise check-node form, log-sum-exp) gives the bound: the
 kernels stay within 4x its own distance from float64, and decide like float64 wherever it does.  Every launch runs on guarded
-operands (tests/guarded.py)."""
-import ctypes as C
-
+operands (tests/guarded.py; the launches themselves are in tests/link_gpu.py)."""
 import numpy as np
 import pytest
 import torch
 
 import link_cases as K
 import link_oracle as O
-from guarded import Guard, ptr as _ptr
+from link_gpu import _code, gpu_decode, gpu_encode, gpu_errors, gpu_llr, gpu_simulate
 
 pytestmark = pytest.mark.gpu
-
-_codes = {}
-
-
-def _code(name):
-    from score_based_channels_amd import link
-    if name not in _codes:
-        H, P, base, Z = K.code(name)
-        c = link.Code(base, Z, K.INTERLEAVER_SEED)
-        assert np.array_equal(c.P, P) and np.array_equal(c.parity_check_matrix(), H)
-        _codes[name] = c
-    return _codes[name]
-
-
-def _lib():
-    from score_based_channels_amd import _lib
-    return _lib
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _rnd(seed=0, snr_index=0, packet0=0, flags=0):
-    return _lib().sbc_link_random(seed=seed, packet0=packet0, snr_index=snr_index, flags=flags)
-
-
-def _c64(g, name, a):
-    return g.inp(name, np.ascontiguousarray(a, np.complex64).view(np.float32).reshape(a.shape + (2,)))
-
-
-def _cplx(t):
-    return np.ascontiguousarray(t.cpu().numpy()).view(np.complex64)[..., 0]
-
-
-def gpu_encode(name, payload, S):
-    L, code, g = _lib(), _code(name), Guard(torch)
-    Npk, (uses, _) = len(payload), _code(name).uses(S)
-    pay = g.inp('payload', np.ascontiguousarray(payload, np.uint8))
-    cw = g.out('codeword', (Npk, code.N), fill=7, dtype=torch.uint8)
-    sym = g.out('symbols', (Npk, uses, S, 2))
-    d = L.sbc_link_encode_desc(payload=_ptr(pay), codeword=_ptr(cw), symbols=_ptr(sym), Npk=Npk, S=S, rnd=_rnd())
-    L.check(L.lib().sbc_link_encode(code.handle('cuda:0'), C.byref(d), _stream()))
-    torch.cuda.synchronize()
-    g.check()
-    return cw.cpu().numpy(), _cplx(sym)
-
-
-def gpu_llr(name, sym, Hp, Hp_est, idx, w, noise_power, clip=True):
-    L, code, g = _lib(), _code(name), Guard(torch)
-    Npk, uses, S = sym.shape
-    pool, Nr, _ = Hp.shape
-    out = [g.out('llr_%s' % k, (Npk, code.N)) for k in ('ideal', 'est')]
-    d = L.sbc_link_llr_desc(symbols=_ptr(_c64(g, 'symbols', sym)), Hp_ideal=_ptr(_c64(g, 'Hp_ideal', Hp)), Hp_est=_ptr(_c64(g, 'Hp_est', Hp_est)),
-                            chan_index=_ptr(g.inp('chan_index', np.ascontiguousarray(idx, np.int32))), noise=_ptr(_c64(g, 'noise', w)),
-                            llr_ideal=_ptr(out[0]), llr_est=_ptr(out[1]), noise_power=noise_power, Npk=Npk, pool=pool, Nr=Nr, S=S,
-                            rnd=_rnd(flags=0 if clip else L.LINK_NO_CLIP))
-    L.check(L.lib().sbc_link_llr(code.handle('cuda:0'), C.byref(d), _stream()))
-    torch.cuda.synchronize()
-    g.check()
-    return out[0].cpu().numpy(), out[1].cpu().numpy()
-
-
-def gpu_decode(name, llr, max_iters, early_stop):
-    L, code, g = _lib(), _code(name), Guard(torch)
-    Npk = len(llr)
-    l = g.inp('llr', np.ascontiguousarray(llr, np.float32))
-    soft, totals = g.out('soft', (Npk, code.K)), g.out('totals', (Npk, code.N))
-    iters = g.out('iters', (Npk,), fill=-1, dtype=torch.int32)
-    L.check(L.lib().sbc_link_decode(code.handle('cuda:0'), _ptr(l), Npk, max_iters, 1 if early_stop else 0, _ptr(soft), _ptr(totals), _ptr(iters),
-                                    _stream()))
-    torch.cuda.synchronize()
-    g.check()
-    return soft.cpu().numpy(), totals.cpu().numpy(), iters.cpu().numpy()
-
-
-def gpu_errors(name, soft, payload):
-    L, code, g = _lib(), _code(name), Guard(torch)
-    Npk = len(soft)
-    ber, bler = g.out('ber', (Npk,)), g.out('bler', (Npk,))
-    L.check(L.lib().sbc_link_errors(code.handle('cuda:0'), _ptr(g.inp('soft', np.ascontiguousarray(soft, np.float32))),
-                                    _ptr(g.inp('payload', np.ascontiguousarray(payload, np.uint8))), Npk, _ptr(ber), _ptr(bler), _stream()))
-    torch.cuda.synchronize()
-    g.check()
-    return ber.cpu().numpy(), bler.cpu().numpy()
-
-
-def gpu_simulate(Hp, Hp_est, noise_power, n, randomness=None, seed=0, snr_index=0, packet0=0):
-    """sbc_link_simulate on the reference code; with ``randomness`` None the draws come from the device streams and are returned."""
-    L, code, g = _lib(), _code('ref'), Guard(torch)
-    pool, Nr, S = Hp.shape
-    uses, _ = code.uses(S)
-    if randomness is None:
-        flags = L.LINK_DEVICE_RANDOM
-        pay = g.out('payload', (n, code.K), fill=7, dtype=torch.uint8)
-        idx = g.out('chan_index', (n, uses), fill=-1, dtype=torch.int32)
-        w = g.out('noise', (n, uses, Nr, 2))
-    else:
-        flags = 0
-        pay = g.inp('payload', np.ascontiguousarray(randomness[0], np.uint8))
-        idx = g.inp('chan_index', np.ascontiguousarray(randomness[1], np.int32))
-        w = _c64(g, 'noise', randomness[2])
-    res = {k: g.out(k, (n,)) for k in ('ber_ideal', 'bler_ideal', 'ber_est', 'bler_est')}
-    res.update({k: g.out(k, (n,), fill=-1, dtype=torch.int32) for k in ('iters_ideal', 'iters_est')})
-    d = L.sbc_link_sim_desc(Hp_ideal=_ptr(_c64(g, 'Hp_ideal', Hp)), Hp_est=_ptr(_c64(g, 'Hp_est', Hp_est)), payload=_ptr(pay), chan_index=_ptr(idx),
-                            noise=_ptr(w), noise_power=noise_power, Npk=n, pool=pool, Nr=Nr, S=S, max_iters=50,
-                            rnd=_rnd(seed, snr_index, packet0, flags), **{k: _ptr(v) for k, v in res.items()})
-    L.check(L.lib().sbc_link_simulate(code.handle('cuda:0'), C.byref(d), _stream()))
-    torch.cuda.synchronize()
-    g.check()
-    out = {k: v.cpu().numpy() for k, v in res.items()}
-    out.update(payload=pay.cpu().numpy(), chan_index=idx.cpu().numpy(), noise=_cplx(w))
-    return out
 
 
 # ---- 1. encoder ------------------------------------------------------------------------------------------------------------------
@@ -143,7 +28,7 @@ def test_encoder_equals_the_restatement_bit_for_bit(name, S):
 
 # ---- 2. soft bits ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('kind', K.LLR_NOISE_KINDS)
-@pytest.mark.parametrize('Nr', [1, 3, 16])
+@pytest.mark.parametrize('Nr', [1, 3, 16, 17, 33, 64])
 @pytest.mark.parametrize('S', [2, 4])
 def test_unclipped_soft_bits_within_four_times_the_float32_restatement(S, Nr, kind):
     """The third noise power puts metric / noise_power ratios above 100: without the subtraction of the smallest metric every fp32
