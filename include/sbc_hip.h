@@ -683,6 +683,59 @@ typedef struct sbc_ls_desc {
 } sbc_ls_desc;
 int sbc_ls_regularized(const sbc_ls_desc* desc, void* stream);
 
+/* sbc_em_gm_amp_run: the EM-GM-AMP baseline of matlab/test_em_gm_amp.m, for every problem b of the batch, all iterations in one
+ * launch (csrc/cs_gamp.hip).  THE LIMIT: the script only calls EMGMAMP(...) from a MATLAB toolbox that is not in the reference's
+ * tree.  The toolbox's source is not available, so its internals -- adaptive step sizes, the order of its EM updates, its
+ * initialisation -- are neither reproduced nor compared against.  Reproduced is the SCRIPT: its operator (:99-101), noise model
+ * (:112-113), schedule (:58-59, :67), configuration and logs (:123-138).  The ALGORITHM is the one defined here, restated from the
+ * published method (Bernoulli Gaussian-mixture GAMP with an EM-learned prior and noise variance); its yardstick is the float64
+ * numpy restatement of this same definition, tests/gamp_oracle.py.
+ *     unknown  X = fft2(H) (:99):  H = Fl X Fr,  Fl = conj(dftmtx(Nt)) / Nt,  Fr = conj(dftmtx(Nr)) / Nr (:37-38);  A1 = P Fl,
+ *              Y = A1 X Fr + noise (:101);  a2 = |A1|^2,  M = Np Nr,  N = Nt Nr
+ *     prior    p(x) = (1 - lam) delta(x) + lam sum_{l=1..4} om_l CN(x; 0, phi_l)  (optEM.heavy_tailed), noise variance psi; one
+ *              parameter set per problem (sig_dim = noise_dim = 'col' on a single column)
+ *     init     lam = Np / (2 Nt);  psi = ||Y||^2 / (101 M);  phibar = (||Y||^2 - M psi) / (||A1||_F^2 lam);  om_l = 1/4;
+ *              phi_l = phibar 4^(l-1) 4/85;  xhat = 0;  taux = lam phibar;  s = 0
+ *     one GAMP iteration (damping theta):
+ *              taup[p] = (1 / Nr^2) sum_i a2[p][i] sum_j taux[i][j];   phat = A1 xhat Fr - taup s
+ *              s_new = (Y - phat) / (taup + psi);  taus_new = 1 / (taup + psi);  zhat = phat + taup s_new;  tauz = taup psi / (taup + psi)
+ *              s <- (1 - theta) s + theta s_new,  taus likewise (the very first iteration of a problem takes the new values undamped)
+ *              taur[i] = Nr / sum_p a2[p][i] taus[p];   rhat = xhat + taur (A1^H s Fr^H)
+ *              denoiser per coefficient, log domain, the largest of the five log-weights subtracted before exp:
+ *                log a_0 = log(1 - lam) - log taur - |rhat|^2 / taur;   log a_l = log(lam om_l) - log(phi_l + taur) - |rhat|^2 / (phi_l + taur)
+ *                beta = a / sum a;  g_l = phi_l / (phi_l + taur);  m_l = phi_l taur / (phi_l + taur) + g_l^2 |rhat|^2
+ *                xhat = sum_l beta_l g_l rhat;   taux = sum_l beta_l m_l - |xhat|^2
+ *     one EM iteration = nit GAMP iterations (xhat, taux, s, taus carry over), then from the last iteration's quantities, with
+ *              pi = sum_{l>=1} beta_l:  lam <- clamp(mean pi, 1/N, 1);  om_l <- sum beta_l / sum pi;
+ *              phi_l <- max(sum beta_l m_l / sum beta_l, 1e-12 phibar) (unchanged where sum beta_l = 0);
+ *              psi <- mean over (p, r) of |Y - zhat|^2 + tauz;   nmse[k][b] = ||Fl xhat Fr - H||^2 / ||H||^2  (complete_log, :127-136)
+ *     stop     with tol > 0 a problem stops after the first EM iteration with ||xhat - xhat_prev||^2 < tol ||xhat||^2 (xhat_prev:
+ *              the end of the EM iteration before, 0 at the start); its remaining nmse rows hold the script's sentinel 1000 (:71),
+ *              stop_iter[b] the number of EM iterations it ran.  tol = 0 never stops.
+ * The whole iteration runs in float64 (products on v_mfma_f64_16x16x4_f64; the iteration is not contractive at fp32 resolution,
+ * DESIGN.md section 18); operands and outputs are fp32, theta and tol are the fp32 values given.  Fixed summation orders, no
+ * atomics: a problem's result is bit-identical whatever the batch and its position in it; NaN / Inf stay inside their problem.
+ * Supported: Nt = 64, Nr = 16, 1 <= Np <= 64, nit >= 1, em_iters >= 1, 0 < theta <= 1; anything else returns SBC_ERR_UNSUPPORTED.
+ * A p_index / h_index entry outside [0, nP) / [0, nH) fills that problem's outputs (where given; stop_iter: -1) with NaN; nothing
+ * is read through the bad index and no other problem is affected.  A refused call (any status but SBC_OK) has written nothing;
+ * B = 0 is SBC_OK and launches nothing.  The first call on a device allocates and uploads two small twiddle tables synchronously
+ * (kept for the life of the process, as sbc_l1_lifted_run keeps its own): that one call is not asynchronous and cannot be captured. */
+typedef struct sbc_em_gm_amp_desc {
+    const float* P;            /* [nP][Np][Nt] pilots, local_P of :81                                                          */
+    const int32_t* p_index;    /* [B] pilot matrix of problem b, or NULL = b                                                   */
+    const float* Y;            /* [B][Np][Nr] noisy measurements, noisy_flat_Y of :112-113 as a matrix                          */
+    const float* Htrue;        /* [nH][Nt][Nr] channels, local_H of :95, or NULL (then nmse must be NULL)                       */
+    const int32_t* h_index;    /* [B] channel of problem b, or NULL = b                                                        */
+    float* nmse;               /* [em_iters][B] NMSE after every EM iteration (complete_log), or NULL                           */
+    float* H_hat;              /* [B][Nt][Nr] final Fl xhat Fr (:118-120), or NULL                                              */
+    float* X;                  /* [B][Nt][Nr] final xhat, or NULL                                                              */
+    float* params;             /* [B][10] final lam, om_1..4, phi_1..4, psi, or NULL                                            */
+    int32_t* stop_iter;        /* [B] EM iterations run, or NULL                                                               */
+    int32_t B, nP, nH, Nt, Nr, Np, nit, em_iters;
+    float theta, tol;          /* damping (0.3); optEM.maxTol (1e-1, :59)                                                       */
+} sbc_em_gm_amp_desc;
+int sbc_em_gm_amp_run(const sbc_em_gm_amp_desc* desc, void* stream);
+
 /* --- Learned D-AMP (the L-DAMP baseline of Fig. 5c) -----------------------------------------------------------------------------
  * src/score_based_channels/test_ldamp.py with aux_models.py:62-190 (LDAMP.forward) and aux_unet.py (FlippedNormUnet), in the
  * configuration train_ldamp.py:41-47 trains: backbone FlippedUNet, one net per unroll (shared_nets = False), chans 16, 3 pools,

@@ -19,6 +19,7 @@ EXPORTS = ('sbc_abi_version', 'sbc_set_persistent_cus', 'sbc_last_error', 'sbc_d
            'sbc_f16x2_calibration_input', 'sbc_f16x2_calibrate', 'sbc_debug_philox4x32', 'sbc_debug_complex_normal',
            'sbc_score_create', 'sbc_score_buffers', 'sbc_score_ops', 'sbc_score_level_source', 'sbc_score_forward',
            'sbc_score_destroy', 'sbc_score_wiring_create', 'sbc_score_wiring_read', 'sbc_score_wiring_destroy', 'sbc_score_wiring_bind', 'sbc_wgrad_scratch_floats', 'sbc_l1_lifted_run', 'sbc_ls_regularized',
+           'sbc_em_gm_amp_run',
            'sbc_ldamp_create', 'sbc_ldamp_destroy', 'sbc_ldamp_workspace_floats', 'sbc_ldamp_denoise', 'sbc_ldamp_run', 'sbc_ldamp_stage',
            'sbc_debug_ldamp_directions',
            'sbc_wgan_create', 'sbc_wgan_destroy', 'sbc_wgan_workspace_floats', 'sbc_wgan_generate', 'sbc_wgan_run', 'sbc_wgan_stage',
@@ -149,6 +150,14 @@ class sbc_ls_desc(C.Structure):
                 ('B', C.c_int32), ('nP', C.c_int32), ('nH', C.c_int32), ('Nt', C.c_int32), ('Nr', C.c_int32), ('Np', C.c_int32)]
 
 
+# EM-GM-AMP (baselines.em_gm_amp)
+class sbc_em_gm_amp_desc(C.Structure):
+    _fields_ = [('P', C.c_void_p), ('p_index', C.c_void_p), ('Y', C.c_void_p), ('Htrue', C.c_void_p), ('h_index', C.c_void_p),
+                ('nmse', C.c_void_p), ('H_hat', C.c_void_p), ('X', C.c_void_p), ('params', C.c_void_p), ('stop_iter', C.c_void_p),
+                ('B', C.c_int32), ('nP', C.c_int32), ('nH', C.c_int32), ('Nt', C.c_int32), ('Nr', C.c_int32), ('Np', C.c_int32),
+                ('nit', C.c_int32), ('em_iters', C.c_int32), ('theta', C.c_float), ('tol', C.c_float)]
+
+
 # Learned D-AMP (ldamp.py)
 class sbc_ldamp_run_desc(C.Structure):
     _fields_ = [('Y_herm', C.c_void_p), ('P_herm', C.c_void_p), ('eig1', C.c_void_p), ('directions', C.c_void_p), ('Htrue', C.c_void_p),
@@ -254,6 +263,7 @@ def lib():
     h.sbc_wgrad_scratch_floats.restype = C.c_int64
     h.sbc_l1_lifted_run.argtypes = [C.POINTER(sbc_l1_lifted_desc), C.c_void_p]
     h.sbc_ls_regularized.argtypes = [C.POINTER(sbc_ls_desc), C.c_void_p]
+    h.sbc_em_gm_amp_run.argtypes = [C.POINTER(sbc_em_gm_amp_desc), C.c_void_p]
     h.sbc_ldamp_create.argtypes = [C.POINTER(sbc_tensor_ref), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     h.sbc_ldamp_destroy.argtypes = [C.c_void_p]
     h.sbc_ldamp_destroy.restype = None

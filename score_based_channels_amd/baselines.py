@@ -1,8 +1,8 @@
-"""Classical channel-estimation baselines of Fig. 5c on the HIP library: Lasso / fsAD (lifted-DFT l1) and ML (regularised
-least squares), batched over independent problems.
+"""Classical channel-estimation baselines of Fig. 5c on the HIP library: Lasso / fsAD (lifted-DFT l1), ML (regularised
+least squares) and EM-GM-AMP, batched over independent problems.
 
-Thin wrappers over ``sbc_l1_lifted_run`` and ``sbc_ls_regularized`` (include/sbc_hip.h).  torch only owns the device memory and
-the stream; every number is computed by the HIP kernels (csrc/cs_l1.hip, csrc/cs_ls.hip).  Shapes, dtypes, indices and values
+Thin wrappers over ``sbc_l1_lifted_run``, ``sbc_ls_regularized`` and ``sbc_em_gm_amp_run`` (include/sbc_hip.h).  torch only owns the
+device memory and the stream; every number is computed by the HIP kernels (csrc/cs_l1.hip, csrc/cs_ls.hip, csrc/cs_gamp.hip).  Shapes, dtypes, indices and values
 are checked here, on the host, before anything is launched.
 
 Layouts (as in the reference scripts): pilots ``P`` ``[nP, Np, Nt]`` (``val_P``, the conj-transposed loader pilots), measurements
@@ -18,6 +18,7 @@ from . import _lib
 
 L1_NT, L1_NR, L1_LIFTINGS = 64, 16, (1, 2, 4)
 LS_MAX_N, LS_MAX_NR, LS_MAX_DIM = 64, 64, 1024
+GAMP_NT, GAMP_NR = 64, 16
 
 
 def _device_of(*tensors):
@@ -120,6 +121,66 @@ def l1_lifted(P, Y, H, lmbda, lr, lifting=4, steps=1000, p_index=None, h_index=N
         for t in (P, Y, H, pidx, hidx, lam, lrt):
             t.record_stream(s)
     return (log, H_hat, X) if want_x else (log, H_hat)
+
+
+def check_em_gm_amp_args(P_shape, Y_shape, H_shape, nit, em_iters, tol, theta):
+    """Host-side checks of ``em_gm_amp`` that need no data: raises ``ValueError`` on everything ``sbc_em_gm_amp_run`` excludes.
+    ``H_shape``: None when there is no reference channel."""
+    if int(nit) != nit or int(nit) < 1:
+        raise ValueError('nit must be an integer >= 1 (got %r)' % (nit,))
+    if int(em_iters) != em_iters or int(em_iters) < 1:
+        raise ValueError('em_iters must be an integer >= 1 (got %r)' % (em_iters,))
+    if not 0 < float(theta) <= 1:
+        raise ValueError('theta must be in (0, 1] (got %r)' % (theta,))
+    if not (np.isfinite(float(tol)) and float(tol) >= 0):
+        raise ValueError('tol must be finite and >= 0 (got %r)' % (tol,))
+    nP, Np, Nt = P_shape
+    B, Npy, Nr = Y_shape
+    if (Nt, Nr) != (GAMP_NT, GAMP_NR):
+        raise ValueError('em_gm_amp supports Nt = %d, Nr = %d (got P %s, Y %s)' % (GAMP_NT, GAMP_NR, P_shape, Y_shape))
+    if H_shape is not None and tuple(H_shape[1:]) != (Nt, Nr):
+        raise ValueError('H must be [nH, %d, %d] (got %s)' % (Nt, Nr, tuple(H_shape)))
+    if Npy != Np or not 1 <= Np <= Nt:
+        raise ValueError('need 1 <= Np <= Nt and Y with the pilots\' Np (got P %s, Y %s)' % (P_shape, Y_shape))
+
+
+def em_gm_amp(P, Y, H, nit=10, em_iters=200, tol=1e-1, theta=0.3, p_index=None, h_index=None, want_x=False, want_params=False,
+              stream=None):
+    """EM-GM-AMP on every problem b (matlab/test_em_gm_amp.m; the algorithm is the one defined in include/sbc_hip.h, restated from the
+    published method -- the MATLAB toolbox the script calls is not reproduced): ``em_iters`` EM iterations of ``nit`` damped GAMP
+    iterations, stopping early per problem at ``tol`` (0: never).  ``H``: the reference channels, or None (then there is no log).
+
+    Returns ``(log, H_hat, stop_iter)`` -- ``log`` float32 ``[em_iters, B]``, the NMSE after every EM iteration that ran and the
+    script's sentinel 1000 behind a stop (None without ``H``); ``H_hat`` complex64 ``[B, Nt, Nr]``; ``stop_iter`` int32 ``[B]``, the EM
+    iterations run -- followed by ``X`` complex64 ``[B, Nt, Nr]`` (the estimate of fft2(H)) when ``want_x`` and by ``params`` float32
+    ``[B, 10]`` (lambda, omega_1..4, phi_1..4, psi) when ``want_params``.  Device tensors; asynchronous on ``stream``."""
+    P, Y = _complex('P', P, 3), _complex('Y', Y, 3)
+    if H is not None:
+        H = _complex('H', H, 3)
+    check_em_gm_amp_args(tuple(P.shape), tuple(Y.shape), tuple(H.shape) if H is not None else None, nit, em_iters, tol, theta)
+    B, nit, em_iters = Y.shape[0], int(nit), int(em_iters)
+    pidx = _index('p_index', p_index, B, P.shape[0])
+    hidx = _index('h_index', h_index, B, H.shape[0]) if H is not None else None
+    device = _device_of(P, Y, H)
+    P, Y, pidx = _upload(device, P), _upload(device, Y), _upload(device, pidx)
+    if H is not None:
+        H, hidx = _upload(device, H), _upload(device, hidx)
+    nt, nr = P.shape[2], Y.shape[2]
+    log = torch.empty((em_iters, B), dtype=torch.float32, device=device) if H is not None else None
+    H_hat = torch.empty((B, nt, nr), dtype=torch.complex64, device=device)
+    stop_iter = torch.empty((B,), dtype=torch.int32, device=device)
+    X = torch.empty((B, nt, nr), dtype=torch.complex64, device=device) if want_x else None
+    params = torch.empty((B, 10), dtype=torch.float32, device=device) if want_params else None
+    d = _lib.sbc_em_gm_amp_desc(P=_ptr(P), p_index=_ptr(pidx), Y=_ptr(Y), Htrue=_ptr(H), h_index=_ptr(hidx), nmse=_ptr(log),
+                                H_hat=_ptr(H_hat), X=_ptr(X), params=_ptr(params), stop_iter=_ptr(stop_iter), B=B, nP=P.shape[0],
+                                nH=H.shape[0] if H is not None else 0, Nt=nt, Nr=nr, Np=P.shape[1], nit=nit, em_iters=em_iters,
+                                theta=float(theta), tol=float(tol))
+    with torch.cuda.device(device):
+        s = stream if stream is not None else torch.cuda.current_stream(device)
+        _lib.check(_lib.lib().sbc_em_gm_amp_run(C.byref(d), C.c_void_p(s.cuda_stream)))
+        for t in (P, Y, pidx) + ((H, hidx) if H is not None else ()):
+            t.record_stream(s)
+    return (log, H_hat, stop_iter) + ((X,) if want_x else ()) + ((params,) if want_params else ())
 
 
 def ls_regularized(P, Y, noise_var, H=None, p_index=None, h_index=None, stream=None):
