@@ -790,6 +790,66 @@ int sbc_ldamp_run(sbc_ldamp* handle, const sbc_ldamp_run_desc* desc, void* strea
 int sbc_ldamp_stage(int32_t stage, int32_t n_images, int64_t* offset, int32_t* channels, int32_t* height, int32_t* width);
 int sbc_debug_ldamp_directions(uint64_t seed, int64_t sample, int32_t unroll, float* out);
 
+/* --- Learned D-AMP training ---------------------------------------------------------------------------------------------------------
+ * src/score_based_channels/train_ldamp.py:107-141 for the configuration above (csrc/ldamp_train.hip): the unrolled forward with every
+ * unroll's activations kept, loss = mean_b sum |h - H|^2 and the logged NMSE = mean_b (sum |h - H|^2 / sum |H|^2), the gradient of the loss
+ * with respect to the 19 tensors of the num_unrolls denoisers that ran, and one step of torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8, no
+ * weight decay).  div and eps are constants of the gradient (aux_models.py:148-171 computes them under no_grad): only the clean
+ * evaluation is differentiated.  The forward is the launches of sbc_ldamp_run, so h, z, div and eps of every unroll are its bits.  Exact
+ * fp32, fixed summation orders, no atomics: the stage gradients of a sample do not depend on B or its position in the batch; a parameter
+ * gradient sums (sample, pixel) pairs in a fixed order.  1 <= B <= 128; all data pointers are DEVICE pointers except where noted.
+ *
+ *   sbc_ldamp_trainer_create            as sbc_ldamp_create; exp_avg, exp_avg_sq and the step count start at 0.  Synchronises.
+ *   sbc_ldamp_trainer_workspace_floats  float32 elements of `workspace` for a step of B samples and num_unrolls unrolls (own_directions != 0:
+ *                                       with room for device-drawn directions); -1 on an argument out of range.  Every unroll keeps its
+ *                                       2B evaluation images and B gradient images: about 1.9 MB per sample and unroll.
+ *   sbc_ldamp_trainer_step              forward, loss, backward and, with step >= 1, the Adam update of nets 0 .. num_unrolls - 1 with learning
+ *                                       rate lr and bias corrections of step `step` (the host counts steps and schedules lr); step = 0:
+ *                                       gradients only.  Launches: 19 per unroll + 1 directions + 1 or 2 copies, 2 for the loss, 54 per unroll
+ *                                       for the backward, 1 Adam.  Asynchronous on `stream`; every argument is checked before anything is
+ *                                       launched; B = 0 launches nothing.
+ *   sbc_ldamp_trainer_adam              the Adam update alone, on `grads` ([n_nets][net floats], tensors in state_dict order; NULL: the
+ *                                       gradients of the last step), for the first n_nets nets.  Asynchronous on `stream`.
+ *   sbc_ldamp_trainer_stage             where a quantity of the last step lies in its workspace, as [n_images][channels][height][width] at
+ *                                       `offset` floats: kind FORWARD (a stage of sbc_ldamp_stage's list, of unroll `unroll`, 2B images), GRAD (the
+ *                                       loss gradient with respect to that stage of the clean evaluation, B images; stage 0: dL/dr, stage 22:
+ *                                       the finish's share of d/d(mean, std)), RSTD (1 / sqrt(var + eps) of a stage's InstanceNorm, [2B][C]), GH
+ *                                       (dL/dh_u as it reaches unroll u, [B][2048]), GZ (dL/dz_u for the z that enters unroll u: the slot has B * 2048 floats per unroll, of which the
+ *                                       first B * Np * 32 hold [B][Np][16][2]), DIV ([B]).
+ *   sbc_ldamp_trainer_get_state /       copy one of: 0 parameters, 1 gradients of the last step, 2 exp_avg, 3 exp_avg_sq ([n_nets][net floats],
+ *   sbc_ldamp_trainer_set_state         tensors in state_dict order, HOST memory) and the step count out of / into the handle.  Synchronise
+ *                                       the device. */
+enum { SBC_LDAMP_TRAIN_FORWARD = 0, SBC_LDAMP_TRAIN_GRAD = 1, SBC_LDAMP_TRAIN_RSTD = 2, SBC_LDAMP_TRAIN_GH = 3, SBC_LDAMP_TRAIN_GZ = 4,
+       SBC_LDAMP_TRAIN_DIV = 5 };
+typedef struct sbc_ldamp_trainer sbc_ldamp_trainer;
+typedef struct sbc_ldamp_step_desc {
+    const float* Y_herm;       /* [B][Np][16] complex                                                                            */
+    const float* P_herm;       /* [B][Np][64] complex                                                                            */
+    const float* eig1;         /* [B]                                                                                            */
+    const float* directions;   /* [num_unrolls][B][64][16][2], or NULL = drawn on the device from (seed, sample0 + b, u)         */
+    const float* Htrue;        /* [B][64][16] complex (sample['H_herm_cplx'])                                                    */
+    float* loss;               /* [2]: loss, NMSE (linear)                                                                       */
+    float* h_log;              /* [num_unrolls][B][64][16] complex, or NULL                                                      */
+    float* z_log;              /* [num_unrolls][B][Np][16] complex, or NULL                                                      */
+    float* div_log;            /* [num_unrolls][B], or NULL                                                                      */
+    float* eps_log;            /* [num_unrolls][B], or NULL                                                                      */
+    float* workspace;          /* sbc_ldamp_trainer_workspace_floats(B, num_unrolls, directions == NULL) floats                  */
+    uint64_t seed;
+    int64_t sample0;
+    double lr;                 /* learning rate of this step                                                                     */
+    int64_t step;              /* 1-based count of this Adam step; 0: no update                                                  */
+    int32_t B, Np, Nt, Nr, num_unrolls;
+} sbc_ldamp_step_desc;
+int sbc_ldamp_trainer_create(const sbc_tensor_ref* tensors, int32_t n_tensors, int32_t n_nets, sbc_ldamp_trainer** out);
+void sbc_ldamp_trainer_destroy(sbc_ldamp_trainer* handle);
+int64_t sbc_ldamp_trainer_workspace_floats(int32_t B, int32_t num_unrolls, int32_t own_directions);
+int sbc_ldamp_trainer_step(sbc_ldamp_trainer* handle, const sbc_ldamp_step_desc* desc, void* stream);
+int sbc_ldamp_trainer_adam(sbc_ldamp_trainer* handle, const float* grads, int32_t n_nets, double lr, int64_t step, void* stream);
+int sbc_ldamp_trainer_stage(int32_t kind, int32_t stage, int32_t unroll, int32_t B, int32_t num_unrolls, int64_t* offset, int32_t* n_images,
+                            int32_t* channels, int32_t* height, int32_t* width);
+int sbc_ldamp_trainer_get_state(sbc_ldamp_trainer* handle, int32_t what, float* out, int64_t* step);
+int sbc_ldamp_trainer_set_state(sbc_ldamp_trainer* handle, int32_t what, const float* in, int64_t step);
+
 /* --- WGAN latent optimisation (the WGAN baseline of Fig. 5c) ---------------------------------------------------------------------
  * src/score_based_channels/test_wgan.py:129-176 with the generator aux_gan.py:58-112 (DCGAN_G_Ours) in eval mode, isize = [16, 64]
  * (Nr, Nt), nz = 60, nc = 2, ngf = 128, L = 2 + n_extra hidden layers, n_extra = 0 .. 4 read from the tensor names (csrc/wgan.hip):

@@ -21,6 +21,8 @@ EXPORTS = ('sbc_abi_version', 'sbc_set_persistent_cus', 'sbc_last_error', 'sbc_d
            'sbc_score_destroy', 'sbc_score_wiring_create', 'sbc_score_wiring_read', 'sbc_score_wiring_destroy', 'sbc_score_wiring_bind', 'sbc_wgrad_scratch_floats', 'sbc_l1_lifted_run', 'sbc_ls_regularized',
            'sbc_em_gm_amp_run',
            'sbc_ldamp_create', 'sbc_ldamp_destroy', 'sbc_ldamp_workspace_floats', 'sbc_ldamp_denoise', 'sbc_ldamp_run', 'sbc_ldamp_stage',
+           'sbc_ldamp_trainer_create', 'sbc_ldamp_trainer_destroy', 'sbc_ldamp_trainer_workspace_floats', 'sbc_ldamp_trainer_step',
+           'sbc_ldamp_trainer_adam', 'sbc_ldamp_trainer_stage', 'sbc_ldamp_trainer_get_state', 'sbc_ldamp_trainer_set_state',
            'sbc_debug_ldamp_directions',
            'sbc_wgan_create', 'sbc_wgan_destroy', 'sbc_wgan_workspace_floats', 'sbc_wgan_generate', 'sbc_wgan_run', 'sbc_wgan_stage',
            'sbc_wgan_trainer_create', 'sbc_wgan_trainer_destroy', 'sbc_wgan_trainer_workspace_floats', 'sbc_wgan_trainer_critic_step',
@@ -166,6 +168,14 @@ class sbc_ldamp_run_desc(C.Structure):
                 ('B', C.c_int32), ('Np', C.c_int32), ('Nt', C.c_int32), ('Nr', C.c_int32), ('num_unrolls', C.c_int32)]
 
 
+# Learned D-AMP training (ldamp.Trainer)
+class sbc_ldamp_step_desc(C.Structure):
+    _fields_ = [('Y_herm', C.c_void_p), ('P_herm', C.c_void_p), ('eig1', C.c_void_p), ('directions', C.c_void_p), ('Htrue', C.c_void_p),
+                ('loss', C.c_void_p), ('h_log', C.c_void_p), ('z_log', C.c_void_p), ('div_log', C.c_void_p), ('eps_log', C.c_void_p),
+                ('workspace', C.c_void_p), ('seed', C.c_uint64), ('sample0', C.c_int64), ('lr', C.c_double), ('step', C.c_int64),
+                ('B', C.c_int32), ('Np', C.c_int32), ('Nt', C.c_int32), ('Nr', C.c_int32), ('num_unrolls', C.c_int32)]
+
+
 # WGAN latent optimisation (wgan.py)
 class sbc_wgan_run_desc(C.Structure):
     _fields_ = [('Y', C.c_void_p), ('P', C.c_void_p), ('H', C.c_void_p), ('z', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p),
@@ -273,6 +283,16 @@ def lib():
     h.sbc_ldamp_run.argtypes = [C.c_void_p, C.POINTER(sbc_ldamp_run_desc), C.c_void_p]
     h.sbc_ldamp_stage.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     h.sbc_debug_ldamp_directions.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_void_p]
+    h.sbc_ldamp_trainer_create.argtypes = [C.POINTER(sbc_tensor_ref), C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    h.sbc_ldamp_trainer_destroy.argtypes = [C.c_void_p]
+    h.sbc_ldamp_trainer_destroy.restype = None
+    h.sbc_ldamp_trainer_workspace_floats.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    h.sbc_ldamp_trainer_workspace_floats.restype = C.c_int64
+    h.sbc_ldamp_trainer_step.argtypes = [C.c_void_p, C.POINTER(sbc_ldamp_step_desc), C.c_void_p]
+    h.sbc_ldamp_trainer_adam.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_void_p]
+    h.sbc_ldamp_trainer_stage.argtypes = [C.c_int32] * 5 + [C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 4
+    h.sbc_ldamp_trainer_get_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]
+    h.sbc_ldamp_trainer_set_state.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
     h.sbc_wgan_create.argtypes = [C.POINTER(sbc_tensor_ref), C.c_int32, C.POINTER(C.c_void_p)]
     h.sbc_wgan_destroy.argtypes = [C.c_void_p]
     h.sbc_wgan_destroy.restype = None
